@@ -5,9 +5,9 @@
 N = 1 (config C2). One *step* = one pairwise combine a = a + b of two 256 MiB float32 peer buckets
 resident in HBM — the reference's `f.f(a, b)` (include/Communicator.h:180-189) on the device, rotating over
 16 buffer sets (8 GiB; the rotation runs on from the warm-up, so no step re-reads a bucket the 256 MB
-Infinity Cache still holds, see --sets). value = 256 MiB / (wall time per step). After the timed region every
-set's bucket is checked bit for bit against numpy's float32 a + b repeated once per launch of that set, on three
-windows (`self_check`); a mismatch prints the line and exits 1.
+Infinity Cache still holds, see --sets). value = 256 MiB / (wall time per step). With --full, after the timed
+region every set's bucket is checked bit for bit against numpy's float32 a + b repeated once per launch of that
+set, on three windows (`self_check`); a mismatch prints the line and exits 1.
 
 N > 1 (config C4's shape at the metric's bucket size). One *step* = the N-peer float32 sum-allreduce of
 256 MiB buckets, ONE FMI peer per GPU (one process per GPU), through the product C-ABI communicator
@@ -15,10 +15,15 @@ fmi_comm_allreduce: all-to-all of N shards over RCCL/xGMI -> the fused N-way ker
 allreduce_no_order order (src/comm/PeerToPeer.cpp:96-130) on every GPU's shard -> all-gather (path TREE,
 bit-identical to the reference's N-peer allreduce). value = N x 256 MiB / (wall time per step, max over
 ranks): reduced bucket bytes delivered per second, summed over the GPUs (weak scaling: 256 MiB per GPU).
-The result of the last timed step is checked on every rank against the single-GPU fused kernel over the same
-synthetic buckets rebuilt locally (`self_check`); a mismatch prints the line and exits 1.
+With --full the result of the last timed step is checked on every rank against the single-GPU fused kernel over
+the same synthetic buckets rebuilt locally (`self_check`); a mismatch prints the line and exits 1.
 
-Also reported (one JSON line on rank 0):
+A run without --full sets up, warms up, times --steps steps and prints the one JSON line (rank 0) with the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`) and the roofline
+taken from events around the timed launches. --dump-outputs DIR writes what the last timed step computed to
+DIR/<name>.npy (N = 1: c2_pair_sum, the in-out bucket; N > 1: allreduce_rank0, rank 0's receive bucket).
+
+Reported with --full only, in the same line:
   roofline      — the dominant HBM kernel: N = 1 the pairwise kernel (3·n·4 bytes per launch), N > 1 the
                   fused N-way shard kernel ((N+1)·shard·4 bytes), duration from HIP events on the library
                   stream it runs on; peak = 8000 GB/s HBM3E; traffic from the committed rocprofv3 PMC summary.
@@ -64,6 +69,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--bucket-mib", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can carry: the in-run self-checks, "
+                         "the isolated kernel timings, the CPU baseline, configs C3 / C4 / C5 and (N>1) the single-GPU "
+                         "anchor and the diagnostics. Without it a run sets up, warms up, times --steps steps and "
+                         "prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a bucket larger than "
+                         "DUMP_MAX_ELEMS elements as a fixed seeded sample of its elements, see dump_indices). The "
+                         "synthetic inputs depend only on the arguments, so two builds can be compared file by file")
     ap.add_argument("--c4-mib", type=int, default=1024, help="N>1: bucket per peer of the c4 block (config C4)")
     ap.add_argument("--sets", type=int, default=16,
                     help="N=1: rotating bucket sets. The pair kernel's sc1 tiles (1 of 8) leave their output lines in "
@@ -385,6 +399,34 @@ def c4_reference(peers: int = 8, mib: int = 1024) -> dict:
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+DUMP_MAX_ELEMS = 1 << 22  # per dumped array: 16 MiB of float32, so a run's dump stays far under 64 MB
+DUMP_SEED = 0x0F31
+
+
+def dump_indices(n: int):
+    """Which elements of an n-element output --dump-outputs keeps: all of them up to DUMP_MAX_ELEMS, else the
+    head and tail windows of 4096 plus DUMP_MAX_ELEMS indices drawn with a fixed seed (sorted, duplicates
+    dropped). A function of n alone, so every run and every build samples the same elements."""
+    import numpy as np
+
+    if n <= DUMP_MAX_ELEMS:
+        return np.arange(n, dtype=np.int64)
+    drawn = np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64)
+    return np.unique(np.concatenate([np.arange(4096, dtype=np.int64), drawn, np.arange(n - 4096, n, dtype=np.int64)]))
+
+
+def dump_output(directory: str, name: str, values) -> str:
+    """--dump-outputs: `values` (a host array, the whole output of the last timed step) as float32 to
+    `directory`/`name`.npy, sampled by dump_indices when large. Returns the path."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    flat = np.asarray(values).reshape(-1)
+    path = os.path.join(directory, name + ".npy")
+    np.save(path, np.ascontiguousarray(flat[dump_indices(flat.size)], dtype=np.float32))
+    return path
+
+
 _JSON_OUT = None
 _LINE_PRINTED = False  # the one JSON line is out (N > 1: by the emitter, on every rank's view)
 _WATCH = None  # N > 1: the phase watch of this rank (names the phase an error line reports)
@@ -554,10 +596,10 @@ def run_single(args):
     nbytes = n * 4
     sets = [tuple(Bucket(n, np.float32).fill_synthetic(42 + s, j) for j in range(2)) for s in range(args.sets)]
     fmi_amd.sync()
-    # self-check windows (head, middle, tail of every set's buckets), read before the first launch
+    # --full: self-check windows (head, middle, tail of every set's buckets), read before the first launch
     win = 4096
     offs = [0, (n // 2) // 64 * 64, n - win]
-    before = [[(a.view(o, win).numpy(), b.view(o, win).numpy()) for o in offs] for a, b in sets]
+    before = [[(a.view(o, win).numpy(), b.view(o, win).numpy()) for o in offs] for a, b in sets] if args.full else None
     launches = [0] * len(sets)
 
     def step(k):  # k runs on from the warm-up, so every set is re-used exactly len(sets) steps later
@@ -580,26 +622,42 @@ def run_single(args):
     t1 = time.perf_counter()
     step_ms = (t1 - t0) * 1e3 / args.steps
     kernel_avg_ms = ev0.elapsed_ms(ev1) / args.steps  # includes the ~1-2 us dispatch gaps between launches
-    # diagnostic, untimed: per-launch event pairs give the launch duration without the gaps
-    probe = min(args.steps, 32)
-    pairs = [(Event(), Event()) for _ in range(probe)]
-    for k in range(probe):
-        pairs[k][0].record()
-        step(args.warmup + args.steps + k)
-        pairs[k][1].record()
-    fmi_amd.sync()
-    isolated_us = 1e3 * sum(a.elapsed_ms(b) for a, b in pairs) / probe
-    check = c2_self_check(sets, offs, win, before, launches)
+    if args.dump_outputs and args.steps > 0:  # what the caller of the last timed combine holds: its in-out bucket
+        dump_output(args.dump_outputs, "c2_pair_sum", sets[(args.warmup + args.steps - 1) % len(sets)][0].numpy())
+    isolated, check = {}, None
+    if args.full:
+        # diagnostic, untimed: per-launch event pairs give the launch duration without the gaps
+        probe = min(args.steps, 32)
+        pairs = [(Event(), Event()) for _ in range(probe)]
+        for k in range(probe):
+            pairs[k][0].record()
+            step(args.warmup + args.steps + k)
+            pairs[k][1].record()
+        fmi_amd.sync()
+        isolated = {"kernel_avg_us_isolated": round(1e3 * sum(a.elapsed_ms(b) for a, b in pairs) / probe, 2)}
+        check = c2_self_check(sets, offs, win, before, launches)
     for a, b in sets:
         a.free()
         b.free()
     roof = _roofline("pair_tile", 3 * nbytes, kernel_avg_ms,
                      "HIP events bracketing the K timed launches on the library stream",
-                     {"kernel_avg_us_isolated": round(isolated_us, 2)}, pmc_key=c2_kernel_signature())
+                     isolated, pmc_key=c2_kernel_signature())
     line = _headline(args, (nbytes / GIB) / (step_ms * 1e-3), step_ms,
                      "C2: 1-GPU pairwise float32 sum-reduce of two 256 MiB device-resident peer buckets",
                      "single GPU (2 peers resident)", n, roof)
     line["config"]["peers"] = 2
+    if args.full:
+        full_single(args, line, check, n)
+    print(json.dumps(line), file=json_out(), flush=True)
+    failed = failed_checks(line)
+    if failed:
+        print("bench: self-check FAILED: " + ", ".join(failed), file=sys.stderr, flush=True)
+        sys.exit(1)
+
+
+def full_single(args, line, check, n) -> None:
+    """--full at N = 1: everything the line carries beside the headline, recorded into `line` — C2's in-run
+    self-check, the P = 1 point of the N > 1 workload, the CPU baseline, configs C3, C4 on one GPU and C5."""
     line["self_check"] = check
     line["allreduce_1peer"] = one_peer_allreduce(n)
     if not args.no_cpu_baseline:
@@ -616,18 +674,14 @@ def run_single(args):
             line["c4_one_gpu"] = f"failed: {type(e).__name__}: {e}"
     if not args.no_c5:
         line["c5"] = c5_single(args.c5_mib)
-    print(json.dumps(line), file=json_out(), flush=True)
-    failed = failed_checks(line)
-    if failed:
-        print("bench: self-check FAILED: " + ", ".join(failed), file=sys.stderr, flush=True)
-        sys.exit(1)
 
 
 def failed_checks(line) -> list:
     """Every in-run check of an N = 1 line that ran and did not pass (C2, the P = 1 allreduce, C3's two kernels,
     C5's three blocks): any of them makes the run exit 1, as the headline's own check does. A block that raised
-    instead of producing a result is reported in the line (its "error"), not counted here."""
-    failed = [] if line["self_check"]["ok"] else ["c2"]
+    instead of producing a result is reported in the line (its "error"), not counted here. A run without --full
+    ran no check and has none to fail."""
+    failed = [] if line.get("self_check", {"ok": True})["ok"] else ["c2"]
     if not line.get("allreduce_1peer", {}).get("result_ok", True):
         failed.append("allreduce_1peer")
     c3 = line.get("c3")
@@ -1340,23 +1394,33 @@ def run_dist(args, world, rank, local_rank):
             return
     out, seed = extra.pop("result")
     value = world * (S / GIB) / (step_ms * 1e-3)
-    watch.enter("self-check")
-    check = ar.self_check(out, n, seed, tolerance=args.path == "rccl")
+    if args.dump_outputs and rank == 0:  # what rank 0's caller of the last timed allreduce holds: its recv bucket
+        watch.enter("dump of the last step's result")
+        dump_output(args.dump_outputs, "allreduce_rank0", out.numpy())
+    check = kern = None
+    if args.full:
+        watch.enter("self-check")
+        check = ar.self_check(out, n, seed, tolerance=args.path == "rccl")
     out.free()
-    watch.enter("isolated shard-kernel timing")
-    kern = ar.shard_kernel(n, launches=max(10, min(args.steps, 50)))
+    if args.full:
+        watch.enter("isolated shard-kernel timing")
+        kern = ar.shard_kernel(n, launches=max(10, min(args.steps, 50)))
     watch.done()
     live = extra.pop("shard_kernel_launches") > 0
     shard_ms = extra.pop("shard_kernel_avg_ms")
-    roof = _roofline("tree_kernel", kern["algorithmic_bytes_per_launch"],
-                     shard_ms if live else kern["kernel_avg_us"] * 1e-3,
-                     ("HIP events recorded by fmi_comm around every shard-kernel launch of the K timed allreduces, "
-                      "on the stream it runs on, mean per launch, max over ranks") if live else
-                     ("HIP events around back-to-back launches of the shard kernel on the library stream after the "
-                      "timed region (N = 1: the allreduce launches no kernel)"),
-                     {"launch_shape": kern["kernel"], "kernel_avg_us_isolated": kern["kernel_avg_us"],
-                      "note": "the allreduce step is xGMI-bound (xgmi_roofline); this is its HBM-bound kernel"},
-                     pmc_key=f"tree_kernel<fmi::dev::OpSum, float, 0, {world}, false>")
+    roof_note = "the allreduce step is xGMI-bound (xgmi_roofline); this is its HBM-bound kernel"
+    if live or kern:
+        roof = _roofline("tree_kernel", (world + 1) * extra["shard_elems"] * 4,
+                         shard_ms if live else kern["kernel_avg_us"] * 1e-3,
+                         ("HIP events recorded by fmi_comm around every shard-kernel launch of the K timed allreduces, "
+                          "on the stream it runs on, mean per launch, max over ranks") if live else
+                         ("HIP events around back-to-back launches of the shard kernel on the library stream after "
+                          "the timed region (N = 1: the allreduce launches no kernel)"),
+                         {"launch_shape": kern["kernel"], "kernel_avg_us_isolated": kern["kernel_avg_us"],
+                          "note": roof_note} if kern else {"note": roof_note},
+                         pmc_key=f"tree_kernel<fmi::dev::OpSum, float, 0, {world}, false>")
+    else:  # the timed allreduces launched no shard kernel (one rank: a copy), and its isolated timing needs --full
+        roof = None
     path_desc = {"tree": "all-to-all + fused tree kernel + all-gather (bit-exact)",
                  "rccl": "RCCL reduce-scatter + all-gather", "direct": "fused tree over IPC-mapped peer windows"}
     line = _headline(args, value, step_ms,
@@ -1373,7 +1437,8 @@ def run_dist(args, world, rank, local_rank):
                            "path": args.path, "transport": args.transport,
                            "algbw_GiB_s": extra["algbw_GiB_s"], "busbw_GiB_s": extra["busbw_GiB_s"],
                            "shard_elems": extra["shard_elems"]})
-    line["self_check"] = check
+    if check is not None:
+        line["self_check"] = check
     if world > 1:
         egress = 2 * (world - 1) * S / world
         xg = egress / (step_ms * 1e-3) / 1e9
@@ -1388,16 +1453,17 @@ def run_dist(args, world, rank, local_rank):
     watchdog = threading.Timer(args.diag_deadline, emit.deadline, args=(state,))
     watchdog.daemon = True
     watchdog.start()
-    try:
-        after_value(args, ar, world, dist, line, proc)
-    except Exception as e:  # never fails the measured line
-        line["after_value_failed"] = f"{type(e).__name__}: {e}"
+    if args.full:
+        try:
+            after_value(args, ar, world, dist, line, proc)
+        except Exception as e:  # never fails the measured line
+            line["after_value_failed"] = f"{type(e).__name__}: {e}"
     emit.emit()
     ar.destroy()
     dist.barrier()
     dist.destroy_process_group()
     watchdog.cancel()
-    if not check["ok"]:
+    if check is not None and not check["ok"]:
         print("bench: self-check FAILED: the sharded allreduce differs from the single-GPU kernel", file=sys.stderr,
               flush=True)
         sys.exit(1)

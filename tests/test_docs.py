@@ -2,7 +2,9 @@
 `fmi_amd/…` path named in DESIGN.md, INTEGRATION.md, README.md and profiles/INDEX.md must match at least one file
 of the tree (a `*` in a cited name is a glob), or be a file of the reference that the text cites as such. Catches
 numbers whose evidence was moved or deleted."""
+import fnmatch
 import glob
+import json
 import os
 import re
 
@@ -11,12 +13,21 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DOCS = ["DESIGN.md", "INTEGRATION.md", "README.md", "profiles/INDEX.md"]
 PATH = re.compile(r"(?<![\w/.])((?:profiles|tools|tests|oracle|include|fmi_amd)/[\w./*{},-]+)")
-REF = "/root/reference"  # read only as a list of its files, to tell a reference citation from a missing file
-REF_ONLY = ("include/comm/", "include/utils/", "include/Communicator.h", "include/fmi.h", "tests/channels.cpp",
-            "tests/communicator.cpp")
+# the reference's own files under include/ and tests/, by name (tests/golden/reference_files.json): tells a
+# citation of the reference from a missing file, wherever the suite runs
+REF_FILES = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_files.json")))["files"]
 # cited in the documents on purpose although not in the tree: removed tools whose history the text points to,
 # and outputs of a local build (gitignored)
-NOT_IN_TREE = {"tools/microbench_scan_lds.hip", "oracle/_ref/libfmi_ref.so", "fmi_amd/lib/libfmi_dev.so"}
+NOT_IN_TREE = {"tools/microbench_scan_lds.hip", "oracle/_ref", "oracle/_ref/libfmi_ref.so",
+               "fmi_amd/lib/libfmi_dev.so"}
+
+
+def _in_reference(pattern):
+    """Does `pattern` (a path; `*` is a glob within one path component) name a file or a directory of the
+    reference?"""
+    want = pattern.split("/")
+    return any(len(want) <= len(have := f.split("/")) and all(fnmatch.fnmatchcase(h, w) for h, w in zip(have, want))
+               for f in REF_FILES)
 
 
 def _expand(p):
@@ -46,10 +57,8 @@ def test_cited_paths_exist(doc):
         p = p.split(":")[0]  # file:line citations
         if any(glob.glob(os.path.join(ROOT, q)) or glob.glob(os.path.join(base, q)) for q in _expand(p)):
             continue
-        if os.path.isdir(REF) and any(glob.glob(os.path.join(REF, q)) for q in _expand(p)):
+        if any(_in_reference(q) for q in _expand(p)):
             continue  # a file of the reference (include/Communicator.h, tests/channels.cpp, ...), cited as such
-        if not os.path.isdir(REF) and p.startswith(REF_ONLY):
-            continue  # no reference checkout here to look in
         if doc.startswith("profiles/") and glob.glob(os.path.join(ROOT, "profiles", "archive", os.path.basename(p))):
             continue
         missing.append(p)

@@ -67,7 +67,7 @@ def test_bench_py_proc_transport(world):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", str(world),
            "--transport", "proc", "--steps", "4", "--warmup", "1", "--dist-sets", "2", "--bucket-mib", "8",
-           "--c4-mib", "16", "--c5-mib", "8", "--diag-deadline", "150"]
+           "--c4-mib", "16", "--c5-mib", "8", "--diag-deadline", "150", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240,
                        env=dict(os.environ, FMI_PROC_TIMEOUT_S="90", OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -114,7 +114,7 @@ def test_bench_py_launches_its_own_ranks():
         env.pop(k, None)
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--transport", "proc", "--steps", "4", "--warmup", "1",
            "--dist-sets", "2", "--bucket-mib", "8", "--c4-mib", "16", "--c5-mib", "8", "--diag-deadline", "150",
-           "--no-diagnostics"]
+           "--no-diagnostics", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = r.stdout.strip().splitlines()
@@ -131,7 +131,7 @@ def test_bench_py_force_dist_rccl_world1():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--force-dist",
            "--steps", "4", "--warmup", "1", "--dist-sets", "2", "--bucket-mib", "8", "--c4-mib", "16",
-           "--c5-mib", "8", "--no-diagnostics"]
+           "--c5-mib", "8", "--no-diagnostics", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240,
                        env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -152,7 +152,7 @@ def test_bench_py_n1_line_self_checks_the_timed_combines():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FMI_BENCH_LAUNCHED"):
         env.pop(k, None)
     cmd = [sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--sets", "4", "--no-cpu-baseline",
-           "--no-c3", "--no-c5"]
+           "--no-c3", "--no-c5", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = r.stdout.strip().splitlines()
@@ -162,6 +162,37 @@ def test_bench_py_n1_line_self_checks_the_timed_combines():
     assert line["n_gpus"] == 1 and line["value"] > 0 and chk["ok"] and chk["mismatches"] == 0
     assert line["workload"] == "local_combine"
     assert chk["elements_checked"] == 4 * 3 * 4096
+
+
+def test_bench_py_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the N = 1 run times its steps and prints the headline alone (no self-check, CPU baseline, C3,
+    C4 or C5 block), and --dump-outputs writes the in-out bucket of the last timed combine: with 1 warm-up and 3
+    timed steps over 2 sets the last step is the second launch on set 1, so the dumped sample (32 MiB bucket:
+    2^23 elements, sampled) must equal (a + b) + b of that set's synthetic buckets in float32, bit for bit."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FMI_BENCH_LAUNCHED"):
+        env.pop(k, None)
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--sets", "2",
+           "--bucket-mib", "32", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240, env=env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(32 / 1024 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert line["roofline"]["kernel_avg_us"] > 0 and "kernel_avg_us_isolated" not in line["roofline"]
+    for block in ("self_check", "allreduce_1peer", "cpu_baseline", "c3", "c4_one_gpu", "c5"):
+        assert block not in line, block
+    import bench
+
+    n = 32 * (1 << 20) // 4
+    idx = bench.dump_indices(n)
+    a, b = (orc.synthetic_at(np.float32, idx, 42 + 1, peer) for peer in (0, 1))
+    got = np.load(os.path.join(str(tmp_path), "c2_pair_sum.npy"))
+    assert got.dtype == np.float32 and os.listdir(str(tmp_path)) == ["c2_pair_sum.npy"]
+    assert np.array_equal(got.view(np.uint32), ((a + b) + b).view(np.uint32))
 
 
 def test_bench_py_error_line_names_the_runtime():
