@@ -33,7 +33,8 @@ from . import _lib  # noqa: E402
 from .device import Alg, DType, Op  # noqa: E402
 
 _TORCH_DTYPE = {torch.float32: DType.F32, torch.float64: DType.F64, torch.int32: DType.I32, torch.int64: DType.I64,
-                torch.int8: DType.I8, torch.uint8: DType.U8, torch.int16: DType.I16}
+                torch.int8: DType.I8, torch.uint8: DType.U8, torch.int16: DType.I16, torch.float16: DType.F16,
+                torch.bfloat16: DType.BF16}
 _REDUCE_OP = {Op.SUM: dist.ReduceOp.SUM, Op.PROD: dist.ReduceOp.PRODUCT, Op.MAX: dist.ReduceOp.MAX,
               Op.MIN: dist.ReduceOp.MIN}
 SHARD_ALIGN = 64  # elements: keeps every shard 256-B aligned for the 16-B vector kernels
@@ -144,7 +145,7 @@ class ShardedAllreduce:
             staging = self._buf("staging", padded, x)
             dist.all_to_all_single(staging, src, group=self.group)
             parts = [staging[j * shard:(j + 1) * shard] for j in range(N)]
-            if op in (Op.MAX, Op.MIN) and x.dtype in (torch.float32, torch.float64):
+            if op in (Op.MAX, Op.MIN) and x.dtype in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
                 # float max / min keep the first operand on ±0 ties and NaNs, so each GPU's peer 2g ends
                 # with its own bits: the shard owner computes the shard in every rank's order and an
                 # all-to-all (instead of the all-gather) delivers rank r's versions (same volume)

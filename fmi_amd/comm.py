@@ -18,7 +18,7 @@ import numpy as np
 
 from ._lib import Timeout  # noqa: F401 - FMI_ERR_TIMEOUT, the reference's FMI::Utils::Timeout
 
-from .device import NP_DTYPE, Alg, Bucket, Op, _sptr, dtype_of
+from .device import Alg, Bucket, Op, _sptr, dtype_of, itemsize_of
 
 ID_BYTES = 128
 
@@ -122,7 +122,7 @@ class Comm:
     def window(self, n: int, dtype) -> Bucket:
         """A symmetric window bucket for Path.DIRECT (collective: every rank, same n and dtype). Release it
         with window_free (collective) or with the communicator."""
-        nbytes = int(n) * np.dtype(NP_DTYPE[dtype_of(dtype)]).itemsize
+        nbytes = int(n) * itemsize_of(dtype)
         p = ctypes.c_void_p()
         _lib.call("fmi_comm_window_alloc", self.handle, nbytes, ctypes.byref(p))
         return Bucket(n, dtype, ptr=p.value)

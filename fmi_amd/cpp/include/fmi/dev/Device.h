@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <limits>
 #include <stdexcept>
 #include <string>
@@ -27,12 +28,101 @@ inline void check(int status, const char* what) {
     if (status != FMI_OK) throw std::runtime_error(std::string(what) + ": " + fmi_last_error());
 }
 
+// The 16-bit float element types (FMI_F16: IEEE binary16; FMI_BF16: the upper 16 bits of binary32) as trivially
+// copyable 2-byte structs over the raw bits, so no host compiler needs _Float16 / __bf16. Arithmetic is the
+// C-ABI's definition (include/fmi_dev.h): widen to float (exact), operate in float, round back to nearest even
+// (subnormals kept, NaN stays NaN); `<` and `==` compare the widened values, so std::max / std::min keep one
+// operand's bits. An FMI user whose buckets are __bf16 / _Float16 binds them by reinterpreting the storage
+// (same size, same bits): see INTEGRATION.md.
+namespace detail {
+inline float bits_to_float(std::uint32_t u) {
+    float f;
+    std::memcpy(&f, &u, sizeof f);
+    return f;
+}
+inline std::uint32_t float_to_bits(float f) {
+    std::uint32_t u;
+    std::memcpy(&u, &f, sizeof u);
+    return u;
+}
+}  // namespace detail
+
+struct bfloat16 {
+    std::uint16_t bits = 0;
+    bfloat16() = default;
+    explicit bfloat16(float f) {
+        const std::uint32_t u = detail::float_to_bits(f);
+        if ((u & 0x7FFFFFFFu) > 0x7F800000u)
+            bits = static_cast<std::uint16_t>((u >> 16) | 0x0040u);  // NaN stays NaN (quieted)
+        else
+            bits = static_cast<std::uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);  // round to nearest even
+    }
+    static bfloat16 from_bits(std::uint16_t b) {
+        bfloat16 x;
+        x.bits = b;
+        return x;
+    }
+    explicit operator float() const { return detail::bits_to_float(static_cast<std::uint32_t>(bits) << 16); }
+};
+
+struct half {
+    std::uint16_t bits = 0;
+    half() = default;
+    explicit half(float f) {
+        const std::uint32_t u = detail::float_to_bits(f);
+        const std::uint32_t sign = (u >> 16) & 0x8000u, mag = u & 0x7FFFFFFFu;
+        if (mag > 0x7F800000u) {
+            bits = static_cast<std::uint16_t>(sign | 0x7E00u | ((mag >> 13) & 0x01FFu));  // NaN stays NaN (quieted)
+        } else if (mag >= 0x47800000u) {  // >= 2^16 (and inf): past the largest finite half even before rounding
+            bits = static_cast<std::uint16_t>(sign | 0x7C00u);
+        } else if (mag >= 0x38800000u) {  // normal half, 2^-14 <= |f|: drop 13 bits, round to nearest even
+            const std::uint32_t v = mag - 0x38000000u;  // rebias 127 -> 15; a carry out of the mantissa bumps the
+            bits = static_cast<std::uint16_t>(sign | ((v + 0x0FFFu + ((v >> 13) & 1u)) >> 13));  // exponent (to inf)
+        } else if (mag < 0x33000000u) {  // < 2^-25: below half of the smallest subnormal
+            bits = static_cast<std::uint16_t>(sign);
+        } else {  // subnormal half: |f| = m * 2^(e-150) with the implicit bit, in units of 2^-24
+            const int e = static_cast<int>(mag >> 23);
+            const std::uint32_t m = (mag & 0x007FFFFFu) | 0x00800000u;
+            const int shift = 126 - e;  // 14..24: m >> shift is |f| / 2^-24
+            const std::uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
+            bits = static_cast<std::uint16_t>(sign | (q + ((rem > halfway || (rem == halfway && (q & 1u))) ? 1u : 0u)));
+        }
+    }
+    static half from_bits(std::uint16_t b) {
+        half x;
+        x.bits = b;
+        return x;
+    }
+    explicit operator float() const {
+        const std::uint32_t sign = static_cast<std::uint32_t>(bits & 0x8000u) << 16;
+        const std::uint32_t e = (bits >> 10) & 0x1Fu, m = bits & 0x03FFu;
+        if (e == 0x1Fu) return detail::bits_to_float(sign | 0x7F800000u | (m << 13));
+        if (e != 0) return detail::bits_to_float(sign | ((e + 112u) << 23) | (m << 13));
+        const float mag = static_cast<float>(m) * 0x1p-24f;  // zero or subnormal: exact
+        return sign ? -mag : mag;
+    }
+};
+
+inline bfloat16 operator+(bfloat16 a, bfloat16 b) { return bfloat16(static_cast<float>(a) + static_cast<float>(b)); }
+inline bfloat16 operator*(bfloat16 a, bfloat16 b) { return bfloat16(static_cast<float>(a) * static_cast<float>(b)); }
+inline bool operator<(bfloat16 a, bfloat16 b) { return static_cast<float>(a) < static_cast<float>(b); }
+inline bool operator==(bfloat16 a, bfloat16 b) { return static_cast<float>(a) == static_cast<float>(b); }
+inline half operator+(half a, half b) { return half(static_cast<float>(a) + static_cast<float>(b)); }
+inline half operator*(half a, half b) { return half(static_cast<float>(a) * static_cast<float>(b)); }
+inline bool operator<(half a, half b) { return static_cast<float>(a) < static_cast<float>(b); }
+inline bool operator==(half a, half b) { return static_cast<float>(a) == static_cast<float>(b); }
+static_assert(sizeof(half) == 2 && sizeof(bfloat16) == 2 && std::is_trivially_copyable_v<half> &&
+                  std::is_trivially_copyable_v<bfloat16>,
+              "16-bit float elements are their raw bits");
+
 // The C-ABI element type of a fundamental A (any integer type by width and signedness, so long long and
-// char map too), or -1: bool, long double and non-arithmetic types stay on the host.
+// char map too) or of Dev::half / Dev::bfloat16, or -1: bool, long double and other types stay on the host.
 template <class A>
 constexpr int dtype_of() {
     if constexpr (std::is_same_v<A, float>) return FMI_F32;
     else if constexpr (std::is_same_v<A, double>) return FMI_F64;
+    else if constexpr (std::is_same_v<A, half>) return FMI_F16;
+    else if constexpr (std::is_same_v<A, bfloat16>) return FMI_BF16;
     else if constexpr (std::is_integral_v<A> && !std::is_same_v<A, bool>) {
         constexpr bool s = std::is_signed_v<A>;
         switch (sizeof(A)) {
@@ -63,7 +153,7 @@ inline void sync() { check(fmi_dev_sync(), "fmi_dev_sync"); }
 // A device-resident bucket of n elements of A (owning, move-only).
 template <class A>
 class Bucket {
-    static_assert(device_type<A>, "device buckets hold float, double or 8/16/32/64-bit integers");
+    static_assert(device_type<A>, "device buckets hold float, double, Dev::half, Dev::bfloat16 or 8/16/32/64-bit integers");
 
 public:
     using value_type = A;

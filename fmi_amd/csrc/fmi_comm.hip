@@ -325,7 +325,8 @@ protected:
     bool aborted_ = false;
 };
 
-// RCCL element type of a dtype; false for the 16-bit integers, which RCCL has no reduction type for.
+// RCCL element type of a dtype (f16 / bf16: ncclFloat16 / ncclBfloat16); false for the 16-bit integers, which RCCL
+// has no reduction type for.
 bool nccl_type(int dtype, ncclDataType_t* t) {
     switch (dtype) {
         case FMI_F32: *t = ncclFloat32; return true;
@@ -336,6 +337,8 @@ bool nccl_type(int dtype, ncclDataType_t* t) {
         case FMI_U64: *t = ncclUint64; return true;
         case FMI_I8: *t = ncclInt8; return true;
         case FMI_U8: *t = ncclUint8; return true;
+        case FMI_F16: *t = ncclFloat16; return true;
+        case FMI_BF16: *t = ncclBfloat16; return true;
         default: return false;
     }
 }

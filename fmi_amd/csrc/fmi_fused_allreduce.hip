@@ -35,8 +35,9 @@ constexpr std::array<FusedFn, sizeof...(I)> all_ranks_table(std::integer_sequenc
 int launch_fused_allreduce_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
     if (P < 2 || P > sched::kMaxFusedPeers)
         return fail(FMI_ERR_INVALID, "all-ranks allreduce kernel needs 2 <= P <= 16, got " + std::to_string(P));
-    return with_op_dtype<false>(op, dtype, [&]<class Op, class T>() -> int {
-        if constexpr (std::is_floating_point_v<T> && (std::is_same_v<Op, OpMax> || std::is_same_v<Op, OpMin>)) {
+    if (is_half_dtype(dtype)) return launch_fused_half_all_ranks(op, dtype, P, ptrs, n, s);
+    return with_op_dtype<kTierCore>(op, dtype, [&]<class Op, class T>() -> int {
+        if constexpr (is_float_elem_v<T> && (std::is_same_v<Op, OpMax> || std::is_same_v<Op, OpMin>)) {
             static constexpr auto table = all_ranks_table<Op, T>(std::make_integer_sequence<int, sched::kMaxFusedPeers - 1>{});
             table[P - 2](ptrs, n, 0, s);
             return check_launch("all-ranks allreduce kernel launch");

@@ -44,19 +44,46 @@ int fused_policy(bool scan, int P);  // FMI_TUNE_FUSED_POLICY: the fused kernels
 
 // The dtypes every kernel is instantiated for (the fused P-way kernels included).
 inline bool is_core_dtype(int dtype) { return dtype >= FMI_F32 && dtype <= FMI_I64; }
+// The 16-bit float dtypes: the pairwise family and the fused allreduce / reduce / scan kernels up to 16 peers.
+inline bool is_half_dtype(int dtype) { return dtype == FMI_F16 || dtype == FMI_BF16; }
 
-// Invoke f.template operator()<T>() for a runtime dtype (ALL: every fmi_dtype_t; else the core four);
-// returns FMI_ERR_INVALID if unknown.
-template <bool ALL, class F>
+// Which (dtype, algorithm, P) have a single-pass kernel (fused, or built from fused blocks): the core dtypes
+// everywhere; the 16-bit floats for allreduce_no_order, reduce_no_order and scan_no_order up to 16 peers. Their
+// left-to-right forms, reduce-partials and P > 16 take run_program_stepwise, like the 8/16-bit integers.
+// `alg`: a sched::Alg (the C-ABI's fmi_alg_t values are its first five).
+inline bool fused_covers(int dtype, int alg, int P) {
+    if (is_core_dtype(dtype)) return true;
+    return is_half_dtype(dtype) && P <= sched::kMaxFusedPeers &&
+           (alg == sched::kAllreduce || alg == sched::kReduce || alg == sched::kScan);
+}
+
+// Dispatch tiers of with_dtype. The fused launch tables are built per tier: the core tier in the translation
+// units that always held them, the half tier in fmi_fused_half_*.hip (launch_fused routes there), so
+// core + half is what a fused launch serves and ALL what the pairwise family serves.
+inline constexpr int kTierCore = 0;  // f32 f64 i32 i64
+inline constexpr int kTierAll = 1;   // every fmi_dtype_t
+inline constexpr int kTierHalf = 2;  // f16 bf16 alone
+
+// Invoke f.template operator()<T>() for a runtime dtype of the tier; returns FMI_ERR_INVALID if it is not in it.
+template <int TIER, class F>
 int with_dtype(int dtype, F&& f) {
-    switch (dtype) {
-        case FMI_F32: return f.template operator()<float>();
-        case FMI_F64: return f.template operator()<double>();
-        case FMI_I32: return f.template operator()<int32_t>();
-        case FMI_I64: return f.template operator()<int64_t>();
-        default: break;
+    if constexpr (TIER != kTierHalf) {
+        switch (dtype) {
+            case FMI_F32: return f.template operator()<float>();
+            case FMI_F64: return f.template operator()<double>();
+            case FMI_I32: return f.template operator()<int32_t>();
+            case FMI_I64: return f.template operator()<int64_t>();
+            default: break;
+        }
     }
-    if constexpr (ALL) {
+    if constexpr (TIER != kTierCore) {
+        switch (dtype) {
+            case FMI_F16: return f.template operator()<_Float16>();
+            case FMI_BF16: return f.template operator()<__bf16>();
+            default: break;
+        }
+    }
+    if constexpr (TIER == kTierAll) {
         switch (dtype) {
             case FMI_U32: return f.template operator()<uint32_t>();
             case FMI_U64: return f.template operator()<uint64_t>();
@@ -71,10 +98,10 @@ int with_dtype(int dtype, F&& f) {
 }
 
 // Invoke f.template operator()<Op, T>() for a runtime (op, dtype); returns FMI_ERR_INVALID if unknown.
-template <bool ALL = true, class F>
+template <int TIER = kTierAll, class F>
 int with_op_dtype(int op, int dtype, F&& f) {
     auto by_dtype = [&]<class Op>() -> int {
-        return with_dtype<ALL>(dtype, [&]<class T>() -> int { return f.template operator()<Op, T>(); });
+        return with_dtype<TIER>(dtype, [&]<class T>() -> int { return f.template operator()<Op, T>(); });
     };
     switch (op) {
         case FMI_OP_SUM: return by_dtype.template operator()<OpSum>();
@@ -90,12 +117,12 @@ inline size_t dtype_size(int dtype) {
         case FMI_F32: case FMI_I32: case FMI_U32: return 4;
         case FMI_F64: case FMI_I64: case FMI_U64: return 8;
         case FMI_I8: case FMI_U8: return 1;
-        case FMI_I16: case FMI_U16: return 2;
+        case FMI_I16: case FMI_U16: case FMI_F16: case FMI_BF16: return 2;
         default: return 0;
     }
 }
 
-inline bool is_float(int dtype) { return dtype == FMI_F32 || dtype == FMI_F64; }
+inline bool is_float(int dtype) { return dtype == FMI_F32 || dtype == FMI_F64 || is_half_dtype(dtype); }
 
 // Fused single-pass launches (P in [2, kMaxFusedPeers], all pointers 16-B aligned). One function per
 // algorithm family, each defined in its own translation unit so the ~1.2k instantiations build in
@@ -121,6 +148,14 @@ int launch_fused_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs,
 int reduce_partials(int op, int dtype, void* const* outs, const void* const* ins, int P, size_t n, hipStream_t s);
 int launch_fused_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+// The 16-bit float instantiations of the launches above (fused_covers), P = 2..16, each family in a translation
+// unit of its own (fmi_fused_half_*.hip); launch_fused and launch_fused_allreduce_all_ranks route to them.
+// rank_aware: the rank-selecting allreduce (float max / min at P != 2^k).
+int launch_fused_half_allreduce(int op, int dtype, bool rank_aware, int P, const PeerPtrs& ptrs, size_t n, int rank,
+                                hipStream_t s);
+int launch_fused_half_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // scans for P = 17..31 (alg = sched::kScan or kScanLtr), reached through the two launches above
 int launch_fused_scan_wide(int op, int dtype, int alg, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // Blocks of a scan beyond 16 peers (sched::kScanCarry / kScanLtrCarry): ptrs.in[0] is the carry, out[0] unused.

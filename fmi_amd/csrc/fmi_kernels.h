@@ -9,7 +9,7 @@
 //   scan_kernel               outs[k]= program_k(x0..x{P-1})   one pass: P reads + P writes
 //   synth_kernel              counter-based synthetic buckets (splitmix64), identical to the host
 //
-// Every access is a 16-B global_load_dwordx4 / global_store_dwordx4 (4 f32/i32 or 2 f64/i64 lanes);
+// Every access is a 16-B global_load_dwordx4 / global_store_dwordx4 (4 f32/i32, 2 f64/i64 or 8 f16/bf16 lanes);
 // the < 16-B remainder of a bucket is handled by the first threads of block 0 with scalar accesses,
 // so a launch never touches a byte outside [0, n).
 #pragma once
@@ -34,6 +34,25 @@ template <class T>
 struct Wrap {
     using type = T;
 };
+// The 16-bit float elements, _Float16 (IEEE binary16) and __bf16 (the upper 16 bits of binary32): one combine
+// widens both operands to f32 (exact), applies the op in f32 and rounds the result back to the storage type
+// (round-to-nearest-even, subnormals kept, NaN stays NaN), after EVERY combine of a P-way program: what the
+// reference's f.f(mine, received) computes at such an element type (std::plus<__bf16>). max / min compare the
+// widened values and keep one operand's 16 bits unchanged.
+template <>
+struct Wrap<_Float16> {
+    using type = float;
+};
+template <>
+struct Wrap<__bf16> {
+    using type = float;
+};
+template <class T>
+inline constexpr bool is_half_float_v = std::is_same_v<T, _Float16> || std::is_same_v<T, __bf16>;
+// "Is a float element" (operand order can change the bits of max / min): the library's own answer, not
+// libstdc++'s, which differs between versions for the two 16-bit types.
+template <class T>
+inline constexpr bool is_float_elem_v = std::is_same_v<T, float> || std::is_same_v<T, double> || is_half_float_v<T>;
 template <>
 struct Wrap<int32_t> {
     using type = uint32_t;
@@ -164,9 +183,63 @@ __device__ __forceinline__ uint32_t combine_bytes(uint32_t a, uint32_t b) {
     }
 }
 
+// 16-bit float lanes, two per 32-bit word, the same bits as Op::apply<T> per element (above).
+// f16 sum / prod: packed math (v_pk_add_f16 / v_pk_mul_f16); it equals the widened form: products are exact in
+// f32, and a sum's f32 intermediate keeps 24 >= 2 * 11 + 2 bits, so rounding twice is rounding once.
+// bf16 sum / prod: the widened form IS the definition: each half to f32 by a shift / a mask, v_pk_add_f32 /
+// v_pk_mul_f32, and both results narrowed by one v_cvt_pk_bf16_f32. max / min: compare per half, keep the
+// operand's own 16 bits.
+using f16x2 = _Float16 __attribute__((ext_vector_type(2)));
+using bf16x2 = __bf16 __attribute__((ext_vector_type(2)));
+using f32x2 = float __attribute__((ext_vector_type(2)));
+
+template <class Op, class T>
+__device__ __forceinline__ uint32_t combine_halves(uint32_t a, uint32_t b) {
+    constexpr bool kSelect = std::is_same_v<Op, OpMax> || std::is_same_v<Op, OpMin>;
+    if constexpr (kSelect) {
+        bool lo, hi;  // take b's half
+        if constexpr (std::is_same_v<T, _Float16>) {
+            const f16x2 x = __builtin_bit_cast(f16x2, a), y = __builtin_bit_cast(f16x2, b);
+            lo = std::is_same_v<Op, OpMax> ? (x.x < y.x) : (y.x < x.x);
+            hi = std::is_same_v<Op, OpMax> ? (x.y < y.y) : (y.y < x.y);
+        } else {
+            const float xl = __builtin_bit_cast(float, a << 16), xh = __builtin_bit_cast(float, a & 0xFFFF0000u);
+            const float yl = __builtin_bit_cast(float, b << 16), yh = __builtin_bit_cast(float, b & 0xFFFF0000u);
+            lo = std::is_same_v<Op, OpMax> ? (xl < yl) : (yl < xl);
+            hi = std::is_same_v<Op, OpMax> ? (xh < yh) : (yh < xh);
+        }
+        return ((lo ? b : a) & 0x0000FFFFu) | ((hi ? b : a) & 0xFFFF0000u);
+    } else if constexpr (std::is_same_v<T, _Float16>) {
+        const f16x2 x = __builtin_bit_cast(f16x2, a), y = __builtin_bit_cast(f16x2, b);
+        if constexpr (std::is_same_v<Op, OpSum>)
+            return __builtin_bit_cast(uint32_t, static_cast<f16x2>(x + y));
+        else
+            return __builtin_bit_cast(uint32_t, static_cast<f16x2>(x * y));
+    } else {
+        f32x2 x, y;
+        x.x = __builtin_bit_cast(float, a << 16);
+        x.y = __builtin_bit_cast(float, a & 0xFFFF0000u);
+        y.x = __builtin_bit_cast(float, b << 16);
+        y.y = __builtin_bit_cast(float, b & 0xFFFF0000u);
+        if constexpr (std::is_same_v<Op, OpSum>)
+            return __builtin_bit_cast(uint32_t, __builtin_convertvector(x + y, bf16x2));
+        else
+            return __builtin_bit_cast(uint32_t, __builtin_convertvector(x * y, bf16x2));
+    }
+}
+
 template <class Op, class T, int W>
 __device__ __forceinline__ Lanes<T, W> combine(const Lanes<T, W>& a, const Lanes<T, W>& b) {
-    if constexpr (sizeof(T) == 1 && W % 4 == 0) {
+    if constexpr (is_half_float_v<T> && W % 2 == 0) {
+        struct Words {
+            uint32_t w[W / 2];
+        };
+        const Words x = __builtin_bit_cast(Words, a), y = __builtin_bit_cast(Words, b);
+        Words r;
+#pragma unroll
+        for (int k = 0; k < W / 2; ++k) r.w[k] = combine_halves<Op, T>(x.w[k], y.w[k]);
+        return __builtin_bit_cast(Lanes<T, W>, r);
+    } else if constexpr (sizeof(T) == 1 && W % 4 == 0) {
         struct Words {
             uint32_t w[W / 4];
         };
@@ -386,11 +459,15 @@ __device__ __forceinline__ Lanes<T, W> opaque(Lanes<T, W> x) {
         uint64_t b = __builtin_bit_cast(uint64_t, x);
         asm("" : "+v"(b));
         return __builtin_bit_cast(Lanes<T, W>, b);
-    } else {
-        static_assert(sizeof(x) == 4, "lane group of 4, 8 or 16 bytes");
+    } else if constexpr (sizeof(x) == 4) {
         uint32_t b = __builtin_bit_cast(uint32_t, x);
         asm("" : "+v"(b));
         return __builtin_bit_cast(Lanes<T, W>, b);
+    } else {
+        static_assert(sizeof(x) == 2, "lane group of 2, 4, 8 or 16 bytes");
+        uint32_t b = __builtin_bit_cast(uint16_t, x);  // one 16-bit float element (the W = 1 tail groups)
+        asm("" : "+v"(b));
+        return __builtin_bit_cast(Lanes<T, W>, static_cast<uint16_t>(b));
     }
 }
 
@@ -527,6 +604,12 @@ __host__ __device__ __forceinline__ T synth_value(uint64_t h) {
         return static_cast<float>(h >> 40) * 0x1p-24f * 2.0f - 1.0f;
     } else if constexpr (std::is_same_v<T, double>) {
         return static_cast<double>(h >> 11) * 0x1p-53 * 2.0 - 1.0;
+    } else if constexpr (std::is_same_v<T, _Float16>) {
+        // multiples of 2^-10 in [-1, 1): exact in f32 and in f16 (at most 11 significant bits)
+        return static_cast<_Float16>(static_cast<float>(h >> 53) * 0x1p-11f * 2.0f - 1.0f);
+    } else if constexpr (std::is_same_v<T, __bf16>) {
+        // multiples of 2^-7 in [-1, 1): exact in f32 and in bf16 (at most 8 significant bits)
+        return static_cast<__bf16>(static_cast<float>(h >> 56) * 0x1p-8f * 2.0f - 1.0f);
     } else {
         // integers: the top 8·sizeof(T) bits of h (i32 = h >> 32, i64 = h, as before)
         using U = std::make_unsigned_t<T>;

@@ -25,8 +25,10 @@ class Op(enum.IntEnum):
 
 
 class DType(enum.IntEnum):
-    """fmi_dtype_t. F32 / F64 / I32 / I64 run every kernel; the other integer widths run the pairwise
-    kernel, and their P-way programs run as pairwise passes."""
+    """fmi_dtype_t. F32 / F64 / I32 / I64 run every kernel. F16 (IEEE binary16) and BF16 (the upper half of
+    binary32) run the pairwise kernels and the fused ALLREDUCE / REDUCE / SCAN kernels up to 16 peers; every
+    combine widens to f32 and rounds back to the storage type (include/fmi_dev.h). The other integer widths
+    run the pairwise kernel; P-way programs without a fused kernel run as pairwise passes."""
     F32 = 0
     F64 = 1
     I32 = 2
@@ -37,6 +39,8 @@ class DType(enum.IntEnum):
     U8 = 7
     I16 = 8
     U16 = 9
+    F16 = 10
+    BF16 = 11
 
 
 class Alg(enum.IntEnum):
@@ -69,7 +73,9 @@ class Tune(enum.IntEnum):
 
 NP_DTYPE = {DType.F32: np.float32, DType.F64: np.float64, DType.I32: np.int32, DType.I64: np.int64,
             DType.U32: np.uint32, DType.U64: np.uint64, DType.I8: np.int8, DType.U8: np.uint8, DType.I16: np.int16,
-            DType.U16: np.uint16}
+            DType.U16: np.uint16, DType.F16: np.float16}
+# numpy has no bfloat16: a BF16 bucket moves its elements' raw bits as np.uint16
+_HOST_DTYPE = {**NP_DTYPE, DType.BF16: np.uint16}
 
 
 def dtype_of(arr_or_dtype) -> DType:
@@ -80,7 +86,14 @@ def dtype_of(arr_or_dtype) -> DType:
     for k, v in NP_DTYPE.items():
         if np.dtype(v) == dt:
             return k
-    raise TypeError(f"unsupported bucket dtype {dt}; FMI device buckets are f32, f64 or 8/16/32/64-bit integers")
+    raise TypeError(f"unsupported bucket dtype {dt}; FMI device buckets are f16, f32, f64 or "
+                    f"8/16/32/64-bit integers (bf16: pass DType.BF16 and move np.uint16 bit patterns)")
+
+
+def itemsize_of(dtype) -> int:
+    """Bytes per element of a numpy dtype or a DType."""
+    dt = dtype if isinstance(dtype, DType) else dtype_of(dtype)
+    return np.dtype(_HOST_DTYPE[dt]).itemsize
 
 
 def _ptr(x) -> Optional[int]:
@@ -134,12 +147,15 @@ def pci_bus_id(device: int) -> str:
 
 
 class Bucket:
-    """A device-resident bucket of `n` elements of `dtype` (owns its HBM allocation unless `view`)."""
+    """A device-resident bucket of `n` elements of `dtype` (owns its HBM allocation unless `view`).
+
+    `dtype` is a numpy dtype or a DType. numpy has no bfloat16, so a bf16 bucket is created with the explicit
+    DType.BF16 and uploads / downloads np.uint16 bit patterns (np.uint16 itself keeps meaning DType.U16)."""
 
     def __init__(self, n: int, dtype, ptr: Optional[int] = None, owner: Optional["Bucket"] = None):
         self.dtype = dtype_of(dtype) if not isinstance(dtype, DType) else dtype
         self.n = int(n)
-        self.itemsize = np.dtype(NP_DTYPE[self.dtype]).itemsize
+        self.itemsize = np.dtype(_HOST_DTYPE[self.dtype]).itemsize
         self._owner = owner
         if ptr is None:
             p = ctypes.c_void_p()
@@ -160,7 +176,7 @@ class Bucket:
         operands): fmi_dev_alloc_group puts bucket j in 4 KiB slot j mod 16, whatever was allocated before
         (DESIGN §4)."""
         dt = dtype_of(dtype) if not isinstance(dtype, DType) else dtype
-        nbytes = int(n) * np.dtype(NP_DTYPE[dt]).itemsize
+        nbytes = int(n) * np.dtype(_HOST_DTYPE[dt]).itemsize
         ptrs = (ctypes.c_void_p * max(int(count), 1))()
         _lib.call("fmi_dev_alloc_group", ptrs, int(count), nbytes)
         out = []
@@ -184,14 +200,14 @@ class Bucket:
         return Bucket(n, self.dtype, ptr=self.ptr + offset * self.itemsize, owner=self)
 
     def upload(self, arr: np.ndarray, stream=None) -> None:
-        arr = np.ascontiguousarray(arr, dtype=NP_DTYPE[self.dtype])
+        arr = np.ascontiguousarray(arr, dtype=_HOST_DTYPE[self.dtype])
         if arr.size != self.n:
             raise ValueError(f"size mismatch: bucket has {self.n} elements, array {arr.size}")
         _lib.call("fmi_dev_h2d_async", self.ptr, arr.ctypes.data, self.nbytes, _sptr(stream))
         _lib.call("fmi_stream_sync", _sptr(stream))
 
     def numpy(self, stream=None) -> np.ndarray:
-        out = np.empty(self.n, dtype=NP_DTYPE[self.dtype])
+        out = np.empty(self.n, dtype=_HOST_DTYPE[self.dtype])
         _lib.call("fmi_dev_d2h_async", out.ctypes.data, self.ptr, self.nbytes, _sptr(stream))
         _lib.call("fmi_stream_sync", _sptr(stream))
         return out

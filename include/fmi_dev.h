@@ -61,10 +61,25 @@ typedef enum { FMI_OP_SUM = 0, FMI_OP_PROD = 1, FMI_OP_MAX = 2, FMI_OP_MIN = 3 }
  * (include/comm/Data.h:50-73); f32 / f64 / i32 / i64 run every kernel, including the fused P-way ones.
  * The other integer widths run the pairwise kernel, and their P-way programs run as pairwise passes in
  * the same order (integer results do not depend on it). Integer sum / prod wrap, as the reference's
- * std::plus / std::multiplies do after conversion back to A. */
+ * std::plus / std::multiplies do after conversion back to A.
+ *
+ * FMI_F16 (IEEE binary16) and FMI_BF16 (the upper 16 bits of binary32). One combine widens both operands to
+ * f32 (exact), applies the op in f32 (round-to-nearest-even, subnormals kept) and narrows the result to the
+ * storage type (round-to-nearest-even, subnormals kept, NaN stays NaN). The result is rounded to the storage
+ * type after EVERY combine of a P-way program, in the program's own order: what the reference's
+ * f.f(mine, received) computes at a 16-bit float element type (std::plus<__bf16>). For bf16 this widened form
+ * is the definition (a correctly rounded bf16 product differs from it deep in the subnormal range); for f16 it
+ * equals native binary16 arithmetic. MAX / MIN are the selections above: the kept operand's 16 bits come out
+ * unchanged (±0, NaN payloads, subnormals). A NaN made by SUM / PROD is some NaN (sign and payload unspecified).
+ * Fused single-pass kernels for the two: fmi_dev_reduce_tree at FMI_ALG_ALLREDUCE / FMI_ALG_REDUCE and
+ * fmi_dev_scan_peers at FMI_ALG_SCAN for 2 <= P <= 16 on 16-B aligned buckets, and with them the shard kernels
+ * of fmi_comm_allreduce / reduce / scan for up to 16 ranks. FMI_ALG_REDUCE_LTR, FMI_ALG_SCAN_LTR, P > 16 and
+ * fmi_comm_reduce_sendbuf's partials run as pairwise passes in the same order (the 16-bit integers' path), bit
+ * for bit the same values; fusing them is left to later work. Additive: fmi_abi_version() stays 1. */
 typedef enum {
     FMI_F32 = 0, FMI_F64 = 1, FMI_I32 = 2, FMI_I64 = 3,
-    FMI_U32 = 4, FMI_U64 = 5, FMI_I8 = 6, FMI_U8 = 7, FMI_I16 = 8, FMI_U16 = 9
+    FMI_U32 = 4, FMI_U64 = 5, FMI_I8 = 6, FMI_U8 = 7, FMI_I16 = 8, FMI_U16 = 9,
+    FMI_F16 = 10, FMI_BF16 = 11
 } fmi_dtype_t;
 
 /* Evaluation orders reproduced by the P-way kernels; each is the combine order of one reference

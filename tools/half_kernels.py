@@ -1,0 +1,121 @@
+"""The 16-bit float kernels against the f32 kernels of equal bytes, on one GPU, timed with events:
+
+  pair     fmi_dev_reduce_pair at 256 MiB per bucket: f32 sum, f16 sum, bf16 sum, bf16 max
+           (3 x 256 MiB algorithmic bytes per launch; 16 rotating sets of two buckets, as bench.py's C2)
+  tree8    the fused 8-way allreduce (fmi_dev_reduce_tree, ALLREDUCE) over a carved group (fmi_dev_alloc_group,
+           8 inputs + the output) at 256 MiB per bucket: f32 sum, bf16 sum
+           (9 x 256 MiB per launch; 3 rotating groups, as bench.py's c4_one_gpu)
+
+Every set is far larger than what the 256 MB Infinity Cache could hold back for its next use. The kernels are
+interleaved, three passes over all of them, so drift of the device hits every kernel alike. One JSON line per
+kernel: bytes/s per pass and their median, the ratio to the f32 kernel of the same family in the same pass, and
+the spread of that f32 kernel against itself over the three passes ((max - min) / median): a 16-bit kernel more
+than that spread below f32 is a finding.
+
+    python3 tools/half_kernels.py [--out profiles/NAME.jsonl]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+import fmi_amd  # noqa: E402
+from fmi_amd import Alg, Bucket, DType, Event, Op  # noqa: E402
+
+MIB = 1 << 20
+PASSES = 3
+DTYPES = {"f32": (np.float32, 4), "f16": (DType.F16, 2), "bf16": (DType.BF16, 2)}
+
+
+def timed(launch, iters, warm):
+    for k in range(warm):
+        launch(k)
+    e0, e1 = Event(), Event()
+    e0.record()
+    for k in range(warm, warm + iters):
+        launch(k)
+    e1.record()
+    e1.sync()
+    ms = e0.elapsed_ms(e1) / iters
+    e0.destroy()
+    e1.destroy()
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mib", type=int, default=256, help="bytes per bucket")
+    ap.add_argument("--iters", type=int, default=32, help="timed launches per kernel and pass")
+    ap.add_argument("--pair-sets", type=int, default=16)
+    ap.add_argument("--tree-sets", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+    fmi_amd.init(0)
+    nbytes = args.mib * MIB
+    P = 8
+
+    pair_sets, groups = {}, {}
+    for name, (dt, esz) in DTYPES.items():
+        n = nbytes // esz
+        pair_sets[name] = [tuple(Bucket(n, dt).fill_synthetic(42 + s, j) for j in range(2)) for s in range(args.pair_sets)]
+    for name in ("f32", "bf16"):
+        dt, esz = DTYPES[name]
+        n = nbytes // esz
+        groups[name] = [Bucket.group(P + 1, n, dt) for _ in range(args.tree_sets)]
+        for g in groups[name]:
+            for p in range(P):
+                g[p].fill_synthetic(11, p)
+    fmi_amd.sync()
+
+    def pair(name, op):
+        sets = pair_sets[name]
+        return lambda k: fmi_amd.reduce_pair(op, *sets[k % len(sets)])
+
+    def tree(name):
+        gs = groups[name]
+        return lambda k: fmi_amd.reduce_tree(Op.SUM, Alg.ALLREDUCE, gs[k % len(gs)][P], gs[k % len(gs)][:P])
+
+    # (kernel, family, the f32 yardstick of the family, launch, algorithmic bytes, warm-up launches)
+    kernels = [("pair f32 sum", "pair", True, pair("f32", Op.SUM), 3 * nbytes, args.pair_sets),
+               ("pair f16 sum", "pair", False, pair("f16", Op.SUM), 3 * nbytes, args.pair_sets),
+               ("pair bf16 sum", "pair", False, pair("bf16", Op.SUM), 3 * nbytes, args.pair_sets),
+               ("pair bf16 max", "pair", False, pair("bf16", Op.MAX), 3 * nbytes, args.pair_sets),
+               ("tree8 f32 sum", "tree8", True, tree("f32"), (P + 1) * nbytes, args.tree_sets),
+               ("tree8 bf16 sum", "tree8", False, tree("bf16"), (P + 1) * nbytes, args.tree_sets)]
+    rates = {k[0]: [] for k in kernels}
+    for _ in range(PASSES):
+        for name, _, _, launch, algo, warm in kernels:
+            ms = timed(launch, args.iters, warm)
+            rates[name].append(algo / (ms * 1e-3))
+    yard = {fam: rates[name] for name, fam, is_yard, *_ in kernels if is_yard}
+    lines = []
+    for name, fam, _, _, algo, _ in kernels:
+        f32 = yard[fam]
+        ratios = [r / y for r, y in zip(rates[name], f32)]
+        lines.append({"tool": "tools/half_kernels.py", "kernel": name, "bucket_mib": args.mib, "algorithmic_bytes": algo,
+                      "iters_per_pass": args.iters, "passes": PASSES,
+                      "rotating_sets": args.pair_sets if fam == "pair" else args.tree_sets,
+                      "GB_s_per_pass": [round(r / 1e9, 1) for r in rates[name]],
+                      "bytes_per_s": round(statistics.median(rates[name])),
+                      "GB_s": round(statistics.median(rates[name]) / 1e9, 1),
+                      "ratio_to_f32_per_pass": [round(x, 4) for x in ratios],
+                      "ratio_to_f32": round(statistics.median(ratios), 4),
+                      "f32_spread": round((max(f32) - min(f32)) / statistics.median(f32), 4),
+                      "timing": "two HIP events around back-to-back launches on the library stream"})
+    out = open(args.out, "a") if args.out else None
+    for line in lines:
+        s = json.dumps(line)
+        print(s, flush=True)
+        if out:
+            out.write(s + "\n")
+    if out:
+        out.close()
+
+
+if __name__ == "__main__":
+    main()
