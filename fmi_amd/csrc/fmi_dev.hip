@@ -309,8 +309,7 @@ int arena_acquire(size_t need, hipStream_t s) {
 size_t arena_stride(size_t n, size_t esz) { return (std::max<size_t>(n * esz, 16) + 255) / 256 * 256; }
 
 // ----------------------------------------------------------------------------------------------------
-// P-way programs for unaligned buckets, the byte/16-bit integer dtypes, the 16-bit floats where no fused kernel
-// exists (fused_covers: left-to-right forms, reduce-partials, P > 16) and the scans beyond 16 peers: the same
+// P-way programs for unaligned buckets and the byte/16-bit integer dtypes (fused_covers): the same
 // schedule, one pairwise pass per step. Only the steps the requested outputs depend on run (an allreduce
 // for one rank needs P - 1 of its P log P steps). Temp buckets live in the arena; slots are assigned on
 // the host (a value's slot is recycled right after its last use) so the arena holds only the peak number
@@ -808,7 +807,7 @@ int reduce_partials(int op, int dtype, void* const* outs, const void* const* ins
     if (n == 0) return FMI_OK;
     bool aligned = true;
     for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]) && aligned16(outs[p]);
-    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned && fused_covers(dtype, sched::kReducePartials, P)) {
+    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned && fused_covers(op, dtype, sched::kReducePartials, P)) {
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) {
             ptrs.in[p] = ins[p];
@@ -1344,7 +1343,7 @@ static int reduce_tree_impl(int op, int dtype, int alg, void* out, const void* c
     for (int t = 0; t < P; ++t) order[t] = ins[alg == FMI_ALG_REDUCE ? (t + rank) % P : t];
     bool aligned = aligned16(out);
     for (int p = 0; p < P; ++p) aligned = aligned && aligned16(order[p]);
-    if (P >= 2 && aligned && fused_covers(dtype, alg, P)) {
+    if (P >= 2 && aligned && fused_covers(op, dtype, alg, P)) {
         if (P > sched::max_fused_peers(alg)) return run_tree_blocked(op, dtype, alg, out, order.data(), P, rank, n, s);
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) ptrs.in[p] = order[p];
@@ -1375,7 +1374,7 @@ static int scan_peers_impl(int op, int dtype, int alg, void* const* outs, const 
     hipStream_t s = resolve(stream);
     bool aligned = true;
     for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]) && aligned16(outs[p]);
-    if (P >= 2 && aligned && fused_covers(dtype, alg, P)) {
+    if (P >= 2 && aligned && fused_covers(op, dtype, alg, P)) {
         if (P > sched::max_fused_peers(alg)) return run_scan_blocked(op, dtype, alg, outs, ins, P, n, s);
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) {

@@ -38,19 +38,12 @@ constexpr std::array<FusedFn, sizeof...(I)> fused_table(std::integer_sequence<in
 // RANK_AWARE: the algorithm hands different operand orders to different peers (allreduce); the
 // rank-selecting kernel is instantiated only where that can change bits (float max/min).
 // [LO, HI]: the peer counts this translation unit instantiates. TIER: the dtypes it instantiates; the core
-// tier hands the 16-bit floats to their own translation units.
+// tier hands the 16-bit floats to their own translation units (launch_fused_half).
 template <int ALG, bool RANK_AWARE, int LO = 2, int HI = sched::kMaxFusedPeers, int TIER = kTierCore>
 int launch_fused(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s) {
     static_assert(2 <= LO && LO <= HI && HI <= sched::max_fused_peers(ALG), "fused peer range");
     if constexpr (TIER == kTierCore) {
-        if (is_half_dtype(dtype)) {
-            if (!fused_covers(dtype, ALG, P))
-                return fail(FMI_ERR_UNSUPPORTED, "no fused kernel for a 16-bit float dtype at algorithm " +
-                                                     std::to_string(ALG) + ", P = " + std::to_string(P));
-            if constexpr (ALG == sched::kAllreduce) return launch_fused_half_allreduce(op, dtype, RANK_AWARE, P, ptrs, n, rank, s);
-            if constexpr (ALG == sched::kReduce) return launch_fused_half_reduce(op, dtype, P, ptrs, n, s);
-            if constexpr (ALG == sched::kScan) return launch_fused_half_scan(op, dtype, P, ptrs, n, s);
-        }
+        if (is_half_dtype(dtype)) return launch_fused_half(ALG, RANK_AWARE, op, dtype, P, ptrs, n, rank, s);
     }
     if (P < LO || P > HI)
         return fail(FMI_ERR_INVALID, "fused kernel needs " + std::to_string(LO) + " <= P <= " + std::to_string(HI) +

@@ -19,6 +19,7 @@
 namespace fmi::dev {
 
 int launch_scan_blocks_one_pass(int op, int dtype, int B, const BlockedScanPtrs& ptrs, size_t n, hipStream_t s) {
+    if (is_half_dtype(dtype)) return launch_scan_blocks_one_pass_half(op, dtype, B, ptrs, n, s);
     if (B > kOnePassScanBlocksNarrow) return launch_scan_blocks_one_pass_wide(op, dtype, B, ptrs, n, s);
     return scan_blocks::launch_range<2, kOnePassScanBlocksNarrow>(op, dtype, B, ptrs, n, s);
 }

@@ -44,17 +44,18 @@ int fused_policy(bool scan, int P);  // FMI_TUNE_FUSED_POLICY: the fused kernels
 
 // The dtypes every kernel is instantiated for (the fused P-way kernels included).
 inline bool is_core_dtype(int dtype) { return dtype >= FMI_F32 && dtype <= FMI_I64; }
-// The 16-bit float dtypes: the pairwise family and the fused allreduce / reduce / scan kernels up to 16 peers.
+// The 16-bit float dtypes: the pairwise family and every fused / one-pass family, each instantiated in the
+// fmi_fused_half_*.hip translation units.
 inline bool is_half_dtype(int dtype) { return dtype == FMI_F16 || dtype == FMI_BF16; }
 
-// Which (dtype, algorithm, P) have a single-pass kernel (fused, or built from fused blocks): the core dtypes
-// everywhere; the 16-bit floats for allreduce_no_order, reduce_no_order and scan_no_order up to 16 peers. Their
-// left-to-right forms, reduce-partials and P > 16 take run_program_stepwise, like the 8/16-bit integers.
+// Which (op, dtype, algorithm, P) have a single-pass kernel (fused, or built from fused blocks): the core dtypes and
+// the 16-bit floats, everywhere. The 8/16-bit integers take run_program_stepwise. No (op, algorithm, P) of the
+// 16-bit floats is held back: none of their kernels needs scratch memory, which is what `op` is
+// here to decide should one ever do.
 // `alg`: a sched::Alg (the C-ABI's fmi_alg_t values are its first five).
-inline bool fused_covers(int dtype, int alg, int P) {
-    if (is_core_dtype(dtype)) return true;
-    return is_half_dtype(dtype) && P <= sched::kMaxFusedPeers &&
-           (alg == sched::kAllreduce || alg == sched::kReduce || alg == sched::kScan);
+inline bool fused_covers(int op, int dtype, int alg, int P) {
+    (void)op, (void)alg, (void)P;
+    return is_core_dtype(dtype) || is_half_dtype(dtype);
 }
 
 // Dispatch tiers of with_dtype. The fused launch tables are built per tier: the core tier in the translation
@@ -63,11 +64,13 @@ inline bool fused_covers(int dtype, int alg, int P) {
 inline constexpr int kTierCore = 0;  // f32 f64 i32 i64
 inline constexpr int kTierAll = 1;   // every fmi_dtype_t
 inline constexpr int kTierHalf = 2;  // f16 bf16 alone
+inline constexpr int kTierF16 = 3;   // one of the two: the largest half-tier programs build one dtype per
+inline constexpr int kTierBF16 = 4;  // translation unit
 
 // Invoke f.template operator()<T>() for a runtime dtype of the tier; returns FMI_ERR_INVALID if it is not in it.
 template <int TIER, class F>
 int with_dtype(int dtype, F&& f) {
-    if constexpr (TIER != kTierHalf) {
+    if constexpr (TIER == kTierCore || TIER == kTierAll) {
         switch (dtype) {
             case FMI_F32: return f.template operator()<float>();
             case FMI_F64: return f.template operator()<double>();
@@ -76,13 +79,10 @@ int with_dtype(int dtype, F&& f) {
             default: break;
         }
     }
-    if constexpr (TIER != kTierCore) {
-        switch (dtype) {
-            case FMI_F16: return f.template operator()<_Float16>();
-            case FMI_BF16: return f.template operator()<__bf16>();
-            default: break;
-        }
-    }
+    if constexpr (TIER == kTierAll || TIER == kTierHalf || TIER == kTierF16)
+        if (dtype == FMI_F16) return f.template operator()<_Float16>();
+    if constexpr (TIER == kTierAll || TIER == kTierHalf || TIER == kTierBF16)
+        if (dtype == FMI_BF16) return f.template operator()<__bf16>();
     if constexpr (TIER == kTierAll) {
         switch (dtype) {
             case FMI_U32: return f.template operator()<uint32_t>();
@@ -148,14 +148,29 @@ int launch_fused_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs,
 int reduce_partials(int op, int dtype, void* const* outs, const void* const* ins, int P, size_t n, hipStream_t s);
 int launch_fused_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// The 16-bit float instantiations of the launches above (fused_covers), P = 2..16, each family in a translation
-// unit of its own (fmi_fused_half_*.hip); launch_fused and launch_fused_allreduce_all_ranks route to them.
+// The 16-bit float instantiations of the launches above (fused_covers), each family in a translation unit of its
+// own (fmi_fused_half_*.hip). launch_fused's core tier hands every 16-bit float launch to launch_fused_half
+// (fmi_fused_half.hip), which picks the unit by (alg, P); launch_fused_allreduce_all_ranks and the one-pass
+// launches below route to theirs themselves.
 // rank_aware: the rank-selecting allreduce (float max / min at P != 2^k).
+int launch_fused_half(int alg, bool rank_aware, int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int rank,
+                      hipStream_t s);
 int launch_fused_half_allreduce(int op, int dtype, bool rank_aware, int P, const PeerPtrs& ptrs, size_t n, int rank,
                                 hipStream_t s);
 int launch_fused_half_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_half_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_half_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_scan_carry(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_scan_ltr_carry(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+// P = 17..31 (one dtype per translation unit) and the 32-input pre-fold block
+int launch_fused_half_allreduce_wide_f16(int op, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
+int launch_fused_half_allreduce_wide_bf16(int op, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
+int launch_fused_half_prefold16(int op, int dtype, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_scan_wide(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_half_scan_ltr_wide(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // scans for P = 17..31 (alg = sched::kScan or kScanLtr), reached through the two launches above
 int launch_fused_scan_wide(int op, int dtype, int alg, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // Blocks of a scan beyond 16 peers (sched::kScanCarry / kScanLtrCarry): ptrs.in[0] is the carry, out[0] unused.
@@ -187,6 +202,15 @@ int launch_chain_one_pass(int op, int dtype, bool scan, int P, const BlockedScan
                           bool carry_in = false);
 int launch_tree_blocks_one_pass(int op, int dtype, int alg, int P, const BlockedScanPtrs& ptrs, size_t n, int rank,
                                 hipStream_t s);
+// The 16-bit float instantiations of the one-pass launches above (arguments already checked by them).
+int launch_chain_one_pass_half(int op, int dtype, bool scan, int P, const BlockedScanPtrs& ptrs, size_t n, hipStream_t s,
+                               bool carry_in);
+int launch_tree_blocks_one_pass_half(int op, int dtype, int alg, int P, const BlockedScanPtrs& ptrs, size_t n, int rank,
+                                     hipStream_t s);
+int launch_prefold_blocks_one_pass_half(int op, int dtype, int P, const BlockedScanPtrs& ptrs, size_t n, int rank_hi,
+                                        hipStream_t s);
+int launch_scan_blocks_one_pass_half(int op, int dtype, int B, const BlockedScanPtrs& ptrs, size_t n, hipStream_t s);
+int launch_scan_blocks_one_pass_half_wide(int op, int dtype, int B, const BlockedScanPtrs& ptrs, size_t n, hipStream_t s);
 
 // Many independent pairwise combines in one launch (fmi_dev_reduce_pair_batch, fmi_pair_batch.hip): up to
 // kPairBatchMax descriptors, every pointer 16-B aligned; workgroup t works on tile t - first_tile[k] of the

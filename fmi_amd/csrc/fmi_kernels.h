@@ -189,11 +189,16 @@ __device__ __forceinline__ uint32_t combine_bytes(uint32_t a, uint32_t b) {
 // bf16 sum / prod: the widened form IS the definition: each half to f32 by a shift / a mask, v_pk_add_f32 /
 // v_pk_mul_f32, and both results narrowed by one v_cvt_pk_bf16_f32. max / min: compare per half, keep the
 // operand's own 16 bits.
+// REWIDEN (bf16 max / min): widen from opaque copies of the two words, so that no widened half can be shared with
+// another combine. Otherwise the compiler keeps the f32 copies of every value that several ranks' expressions of a
+// rank-selecting kernel reuse next to the packed words: 256 VGPRs + 256 AGPRs and 20-24 bytes of scratch per lane
+// from 26 peers on; re-widening, P = 31 takes 256 + 48 and no scratch. Only there: these kernels are bound by VALU
+// work, and redoing the shifts and masks costs more than the AGPR copies (kRewidenFused below).
 using f16x2 = _Float16 __attribute__((ext_vector_type(2)));
 using bf16x2 = __bf16 __attribute__((ext_vector_type(2)));
 using f32x2 = float __attribute__((ext_vector_type(2)));
 
-template <class Op, class T>
+template <class Op, class T, bool REWIDEN = false>
 __device__ __forceinline__ uint32_t combine_halves(uint32_t a, uint32_t b) {
     constexpr bool kSelect = std::is_same_v<Op, OpMax> || std::is_same_v<Op, OpMin>;
     if constexpr (kSelect) {
@@ -203,8 +208,13 @@ __device__ __forceinline__ uint32_t combine_halves(uint32_t a, uint32_t b) {
             lo = std::is_same_v<Op, OpMax> ? (x.x < y.x) : (y.x < x.x);
             hi = std::is_same_v<Op, OpMax> ? (x.y < y.y) : (y.y < x.y);
         } else {
-            const float xl = __builtin_bit_cast(float, a << 16), xh = __builtin_bit_cast(float, a & 0xFFFF0000u);
-            const float yl = __builtin_bit_cast(float, b << 16), yh = __builtin_bit_cast(float, b & 0xFFFF0000u);
+            uint32_t wa = a, wb = b;
+            if constexpr (REWIDEN) {
+                asm("" : "+v"(wa));
+                asm("" : "+v"(wb));
+            }
+            const float xl = __builtin_bit_cast(float, wa << 16), xh = __builtin_bit_cast(float, wa & 0xFFFF0000u);
+            const float yl = __builtin_bit_cast(float, wb << 16), yh = __builtin_bit_cast(float, wb & 0xFFFF0000u);
             lo = std::is_same_v<Op, OpMax> ? (xl < yl) : (yl < xl);
             hi = std::is_same_v<Op, OpMax> ? (xh < yh) : (yh < xh);
         }
@@ -228,7 +238,7 @@ __device__ __forceinline__ uint32_t combine_halves(uint32_t a, uint32_t b) {
     }
 }
 
-template <class Op, class T, int W>
+template <class Op, class T, int W, bool REWIDEN = false>
 __device__ __forceinline__ Lanes<T, W> combine(const Lanes<T, W>& a, const Lanes<T, W>& b) {
     if constexpr (is_half_float_v<T> && W % 2 == 0) {
         struct Words {
@@ -237,7 +247,7 @@ __device__ __forceinline__ Lanes<T, W> combine(const Lanes<T, W>& a, const Lanes
         const Words x = __builtin_bit_cast(Words, a), y = __builtin_bit_cast(Words, b);
         Words r;
 #pragma unroll
-        for (int k = 0; k < W / 2; ++k) r.w[k] = combine_halves<Op, T>(x.w[k], y.w[k]);
+        for (int k = 0; k < W / 2; ++k) r.w[k] = combine_halves<Op, T, REWIDEN>(x.w[k], y.w[k]);
         return __builtin_bit_cast(Lanes<T, W>, r);
     } else if constexpr (sizeof(T) == 1 && W % 4 == 0) {
         struct Words {
@@ -435,9 +445,17 @@ inline constexpr int kOut = sched::Fused<ALG, P>::prog.out[R];
 template <int ALG, int P>
 inline constexpr int kNumSteps = sched::Fused<ALG, P>::prog.nsteps;
 
-template <class Op, class T, int W, int ALG, int P, size_t... S>
+// The rank-selecting kernels (ALL_RANKS) evaluate every rank's expression. Their bf16 max / min combines re-widen
+// (combine_halves) from kRewidenMinPeers peers on, where the shared widened copies no longer fit the register file
+// (max spills from 26 peers, min from 30). Below, sharing them is faster: the 24-peer kernel runs at 0.48 of the
+// f32 kernel's rate against 0.41 re-widening.
+inline constexpr int kRewidenMinPeers = 26;
+template <class T, bool ALL_RANKS, int P>
+inline constexpr bool kRewidenFused = ALL_RANKS && std::is_same_v<T, __bf16> && P >= kRewidenMinPeers;
+
+template <class Op, class T, int W, int ALG, int P, bool REWIDEN = false, size_t... S>
 __device__ __forceinline__ void run_steps(Lanes<T, W>* v, std::index_sequence<S...>) {
-    ((v[P + S] = combine<Op, T, W>(v[kStepA<ALG, P, S>], v[kStepB<ALG, P, S>])), ...);
+    ((v[P + S] = combine<Op, T, W, REWIDEN>(v[kStepA<ALG, P, S>], v[kStepB<ALG, P, S>])), ...);
 }
 
 template <class T, int W, int P, size_t... I>
@@ -496,7 +514,7 @@ template <class Op, class T, int ALG, int P, bool ALL_RANKS, int W>
 __device__ __forceinline__ void tree_group(const PeerPtrs& ptrs, int rank, size_t elem) {
     Lanes<T, W> v[P + kNumSteps<ALG, P>];
     load_peers<T, W, P>(v, ptrs, elem, std::make_index_sequence<P>{});
-    run_steps<Op, T, W, ALG, P>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
+    run_steps<Op, T, W, ALG, P, kRewidenFused<T, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
     Lanes<T, W> r;
     if constexpr (ALL_RANKS)
         r = pick_rank<T, W, ALG, P>(v, rank, std::make_index_sequence<P>{});
@@ -509,7 +527,7 @@ template <class Op, class T, int ALG, int P, bool ALL_RANKS, int W>
 __device__ __forceinline__ void tree_group_tile(const PeerPtrs& ptrs, int rank, size_t tile_byte, unsigned lane_byte) {
     Lanes<T, W> v[P + kNumSteps<ALG, P>];
     load_peers_tile<T, W, P>(v, ptrs, tile_byte, lane_byte, std::make_index_sequence<P>{});
-    run_steps<Op, T, W, ALG, P>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
+    run_steps<Op, T, W, ALG, P, kRewidenFused<T, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
     Lanes<T, W> r;
     if constexpr (ALL_RANKS)
         r = pick_rank<T, W, ALG, P>(v, rank, std::make_index_sequence<P>{});

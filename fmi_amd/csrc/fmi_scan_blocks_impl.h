@@ -115,13 +115,13 @@ void blocks_one(const BlockedScanPtrs& ptrs, size_t n, hipStream_t s) {
 }
 
 
-// Launch table for B in [LO, HI] full blocks.
-template <int LO, int HI>
+// Launch table for B in [LO, HI] full blocks, for the dtypes of one tier.
+template <int LO, int HI, int TIER = kTierCore>
 int launch_range(int op, int dtype, int B, const BlockedScanPtrs& ptrs, size_t n, hipStream_t s) {
     if (B < LO || B > HI)
         return fail(FMI_ERR_INVALID, "one-pass blocked scan: B = " + std::to_string(B) + " outside [" +
                                          std::to_string(LO) + ", " + std::to_string(HI) + "]");
-    return with_op_dtype<false>(op, dtype, [&]<class Op, class T>() -> int {
+    return with_op_dtype<TIER>(op, dtype, [&]<class Op, class T>() -> int {
         static constexpr auto table = []<int... I>(std::integer_sequence<int, I...>) {
             return std::array<BlocksFn, sizeof...(I)>{&blocks_one<Op, T, I + LO>...};
         }(std::make_integer_sequence<int, HI - LO + 1>{});

@@ -25,10 +25,10 @@ class Op(enum.IntEnum):
 
 
 class DType(enum.IntEnum):
-    """fmi_dtype_t. F32 / F64 / I32 / I64 run every kernel. F16 (IEEE binary16) and BF16 (the upper half of
-    binary32) run the pairwise kernels and the fused ALLREDUCE / REDUCE / SCAN kernels up to 16 peers; every
-    combine widens to f32 and rounds back to the storage type (include/fmi_dev.h). The other integer widths
-    run the pairwise kernel; P-way programs without a fused kernel run as pairwise passes."""
+    """fmi_dtype_t. F32 / F64 / I32 / I64 run every kernel, and so do F16 (IEEE binary16) and BF16 (the upper half
+    of binary32): the pairwise kernels and every fused / one-pass P-way form, at all five algorithms and any number
+    of peers; every combine widens to f32 and rounds back to the storage type (include/fmi_dev.h). The other integer
+    widths run the pairwise kernel, and their P-way programs run as pairwise passes (as unaligned buckets do)."""
     F32 = 0
     F64 = 1
     I32 = 2

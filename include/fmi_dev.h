@@ -71,11 +71,11 @@ typedef enum { FMI_OP_SUM = 0, FMI_OP_PROD = 1, FMI_OP_MAX = 2, FMI_OP_MIN = 3 }
  * is the definition (a correctly rounded bf16 product differs from it deep in the subnormal range); for f16 it
  * equals native binary16 arithmetic. MAX / MIN are the selections above: the kept operand's 16 bits come out
  * unchanged (±0, NaN payloads, subnormals). A NaN made by SUM / PROD is some NaN (sign and payload unspecified).
- * Fused single-pass kernels for the two: fmi_dev_reduce_tree at FMI_ALG_ALLREDUCE / FMI_ALG_REDUCE and
- * fmi_dev_scan_peers at FMI_ALG_SCAN for 2 <= P <= 16 on 16-B aligned buckets, and with them the shard kernels
- * of fmi_comm_allreduce / reduce / scan for up to 16 ranks. FMI_ALG_REDUCE_LTR, FMI_ALG_SCAN_LTR, P > 16 and
- * fmi_comm_reduce_sendbuf's partials run as pairwise passes in the same order (the 16-bit integers' path), bit
- * for bit the same values; fusing them is left to later work. Additive: fmi_abi_version() stays 1. */
+ * The two have every single-pass kernel f32 has: fmi_dev_reduce_tree and fmi_dev_scan_peers at all five algorithms
+ * and any P on 16-B aligned buckets (fused up to 31 peers, the one-pass chains, blocked trees, pre-fold allreduces
+ * and blocked scans beyond, superblocks past 128), and with them the shard kernels of fmi_comm_allreduce / reduce /
+ * scan and fmi_comm_reduce_sendbuf's partials at any number of ranks. Only unaligned buckets run as pairwise passes
+ * in the same order (the 16-bit integers' path), bit for bit the same values. Additive: fmi_abi_version() stays 1. */
 typedef enum {
     FMI_F32 = 0, FMI_F64 = 1, FMI_I32 = 2, FMI_I64 = 3,
     FMI_U32 = 4, FMI_U64 = 5, FMI_I8 = 6, FMI_U8 = 7, FMI_I16 = 8, FMI_U16 = 9,
@@ -172,10 +172,15 @@ int fmi_event_elapsed_ms(float* ms, fmi_event_t start, fmi_event_t stop);
  * recorded once and replayed as one submission. Between capture_begin and capture_end on a stream made by
  * fmi_stream_create, calls on that stream are recorded, not run. Capture-safe: fmi_dev_reduce_pair,
  * fmi_dev_combine, the d2d / memset copies, and fmi_dev_reduce_tree / fmi_dev_scan_peers up to 16 peers
- * (one fused kernel each). Everything else (host-ingress paths, communicators, P > 16 programs, which
- * may allocate or synchronise) is not: that call or capture_end fails, the graph is discarded, and the
- * stream must be destroyed and replaced (HIP leaves a stream whose capture was invalidated unusable).
- * Pointers and sizes are frozen in the graph; replays recompute the same buckets. */
+ * (one fused kernel each) on 16-B aligned f32 / f64 / i32 / i64 / f16 / bf16 buckets, at every algorithm: for
+ * FMI_F16 / FMI_BF16 that includes FMI_ALG_REDUCE_LTR and FMI_ALG_SCAN_LTR. Beyond 16 peers a call on such buckets
+ * is capture-safe exactly where it needs no temporary bucket, which at FMI_TUNE_BLOCKS_ONE_PASS = 1 (the default)
+ * is, the same for the six dtypes: FMI_ALG_ALLREDUCE at P <= 31 and P = 32, 48, 64, 80, 96, 112; FMI_ALG_REDUCE at
+ * P <= 128; FMI_ALG_SCAN at P <= 143; FMI_ALG_SCAN_LTR at any P; FMI_ALG_REDUCE_LTR at P <= 128, and beyond when
+ * `out` is none of ins[128..P). Everything else (host-ingress paths, communicators, other P-way programs, unaligned
+ * buckets and the 8/16-bit integers at P > 1, which may allocate or synchronise) is not: that call or capture_end
+ * fails, the graph is discarded, and the stream must be destroyed and replaced (HIP leaves a stream whose capture
+ * was invalidated unusable). Pointers and sizes are frozen in the graph; replays recompute the same buckets. */
 typedef void* fmi_graph_t;
 int fmi_graph_capture_begin(fmi_stream_t stream);
 int fmi_graph_capture_end(fmi_stream_t stream, fmi_graph_t* graph);
@@ -216,7 +221,8 @@ int fmi_dev_combine(int op, int dtype, void* out, const void* a, const void* b, 
  * reference). One fused kernel (a single
  * pass over the P buckets) for P <= 16, and for ALLREDUCE up to 31; larger P as fused sub-programs of the
  * identical order over blocks of 16 peers (every input read once, plus one write and one read per block
- * value). Unaligned buckets and the 8/16-bit dtypes run the same order as pairwise passes. */
+ * value). The single-pass kernels exist for f32 / f64 / i32 / i64 / f16 / bf16; unaligned buckets and the 8/16-bit
+ * integers run the same order as pairwise passes. */
 int fmi_dev_reduce_tree(int op, int dtype, int alg, void* out, const void* const* ins, int P, int rank,
                         size_t n, fmi_stream_t stream);
 
@@ -225,7 +231,8 @@ int fmi_dev_reduce_tree(int op, int dtype, int alg, void* out, const void* const
  * (src/comm/PeerToPeer.cpp:154-184, :141-152) and Communicator::scan (include/Communicator.h:135-150)
  * when the P buckets sit on one device. outs[k] may alias ins[k]. Any P >= 1: one fused pass up to 31
  * peers; beyond, every input is read at most twice (block totals, then the blocks continued from their
- * carry). */
+ * carry). The same dtypes as fmi_dev_reduce_tree have these kernels (f16 / bf16 included, at both algorithms);
+ * unaligned buckets and the 8/16-bit integers run the same order as pairwise passes. */
 int fmi_dev_scan_peers(int op, int dtype, int alg, void* const* outs, const void* const* ins, int P,
                        size_t n, fmi_stream_t stream);
 

@@ -6,6 +6,19 @@
            8 inputs + the output) at 256 MiB per bucket: f32 sum, bf16 sum
            (9 x 256 MiB per launch; 3 rotating groups, as bench.py's c4_one_gpu)
 
+With --forms, the fused forms beyond the 8-way allreduce instead, each family allocated, measured and freed in turn:
+
+  reduce_ltr8   REDUCE_LTR over 8 peers: f32 sum, bf16 sum              (9 x 256 MiB per launch; 3 groups)
+  scan_ltr8     SCAN_LTR over 8 peers: f32 sum, bf16 sum                (16 x 256 MiB; 3 groups)
+  reduce32      REDUCE over 32 peers: f32 sum, bf16 sum, f32 max, f16 max (33 x 256 MiB; 2 groups)
+  allreduce24   ALLREDUCE over 24 peers, rank 17 (float max: the rank-selecting kernel): f32 max, bf16 max
+                                                                        (25 x 256 MiB; 2 groups)
+  scan32        SCAN over 32 peers: f32 sum, bf16 sum                   (64 x 256 MiB; 2 groups)
+  allreduce13   (only with --only) ALLREDUCE over 13 peers, rank 5: f32 max, bf16 max (14 x 256 MiB; 3 groups)
+
+The yardstick of a 16-bit kernel is the f32 kernel of the same family and op. The same rows run against any
+library (FMI_DEV_LIB), e.g. one built from an earlier commit whose 16-bit programs ran as pairwise passes.
+
 Every set is far larger than what the 256 MB Infinity Cache could hold back for its next use. The kernels are
 interleaved, three passes over all of them, so drift of the device hits every kernel alike. One JSON line per
 kernel: bytes/s per pass and their median, the ratio to the f32 kernel of the same family in the same pass, and
@@ -13,6 +26,7 @@ the spread of that f32 kernel against itself over the three passes ((max - min) 
 than that spread below f32 is a finding.
 
     python3 tools/half_kernels.py [--out profiles/NAME.jsonl]
+    python3 tools/half_kernels.py --forms [--only reduce_ltr8,reduce32] [--label NAME] [--out profiles/NAME.jsonl]
 """
 import argparse
 import json
@@ -47,6 +61,78 @@ def timed(launch, iters, warm):
     return ms
 
 
+def emit(lines, path):
+    out = open(path, "a") if path else None
+    for line in lines:
+        s = json.dumps(line)
+        print(s, flush=True)
+        if out:
+            out.write(s + "\n")
+    if out:
+        out.close()
+
+
+# family: (peers, buckets per group, rotating groups, launch(op, group), [(dtype, op, the f32 yardstick's name)])
+def _reduce(alg, P, rank=0):
+    return lambda op, g: fmi_amd.reduce_tree(op, alg, g[P], g[:P], rank=rank)
+
+
+def _scan(alg, P):
+    return lambda op, g: fmi_amd.scan_peers(op, alg, g[P:], g[:P])
+
+
+FORMS = {
+    "reduce_ltr8": (8, 9, 3, _reduce(Alg.REDUCE_LTR, 8), [("f32", "sum"), ("bf16", "sum")]),
+    "scan_ltr8": (8, 16, 3, _scan(Alg.SCAN_LTR, 8), [("f32", "sum"), ("bf16", "sum")]),
+    "reduce32": (32, 33, 2, _reduce(Alg.REDUCE, 32), [("f32", "sum"), ("bf16", "sum"), ("f32", "max"), ("f16", "max")]),
+    "allreduce24": (24, 25, 2, _reduce(Alg.ALLREDUCE, 24, rank=17), [("f32", "max"), ("bf16", "max")]),
+    "scan32": (32, 64, 2, _scan(Alg.SCAN, 32), [("f32", "sum"), ("bf16", "sum")]),
+    # not in the default set (--only allreduce13): the rank-selecting kernel below 17 peers
+    "allreduce13": (13, 14, 3, _reduce(Alg.ALLREDUCE, 13, rank=5), [("f32", "max"), ("bf16", "max")]),
+}
+OPS = {"sum": Op.SUM, "max": Op.MAX}
+
+
+def forms(args):
+    nbytes = args.mib * MIB
+    for fam in (args.only.split(",") if args.only else [f for f in FORMS if f != "allreduce13"]):
+        P, count, sets, launch, rows = FORMS[fam]
+        groups = {}
+        for name in {r[0] for r in rows}:
+            dt, esz = DTYPES[name]
+            groups[name] = [Bucket.group(count, nbytes // esz, dt) for _ in range(sets)]
+            for g in groups[name]:
+                for p in range(P):
+                    g[p].fill_synthetic(11, p)
+        fmi_amd.sync()
+        rates = {r: [] for r in rows}
+        for _ in range(PASSES):
+            for name, op in rows:
+                gs = groups[name]
+                ms = timed(lambda k: launch(OPS[op], gs[k % len(gs)]), args.iters, sets)
+                rates[(name, op)].append(count * nbytes / (ms * 1e-3))
+        lines = []
+        for name, op in rows:
+            f32 = rates[("f32", op)]
+            ratios = [r / y for r, y in zip(rates[(name, op)], f32)]
+            lines.append({"tool": "tools/half_kernels.py --forms", "label": args.label, "kernel": f"{fam} {name} {op}",
+                          "peers": P, "bucket_mib": args.mib, "algorithmic_bytes": count * nbytes,
+                          "iters_per_pass": args.iters, "passes": PASSES, "rotating_sets": sets,
+                          "GB_s_per_pass": [round(r / 1e9, 1) for r in rates[(name, op)]],
+                          "bytes_per_s": round(statistics.median(rates[(name, op)])),
+                          "GB_s": round(statistics.median(rates[(name, op)]) / 1e9, 1),
+                          "ratio_to_f32_per_pass": [round(x, 4) for x in ratios],
+                          "ratio_to_f32": round(statistics.median(ratios), 4),
+                          "f32_spread": round((max(f32) - min(f32)) / statistics.median(f32), 4),
+                          "timing": "two HIP events around back-to-back launches on the library stream"})
+        emit(lines, args.out)
+        for gs in groups.values():
+            for g in gs:
+                for b in g:
+                    b.free()
+        fmi_amd.sync()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256, help="bytes per bucket")
@@ -54,8 +140,13 @@ def main():
     ap.add_argument("--pair-sets", type=int, default=16)
     ap.add_argument("--tree-sets", type=int, default=3)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--forms", action="store_true", help="the fused forms (see above) instead of pair / tree8")
+    ap.add_argument("--only", default=None, help="with --forms: a comma-separated subset of the families")
+    ap.add_argument("--label", default="tree", help="with --forms: what the lines are tagged with (e.g. the commit)")
     args = ap.parse_args()
     fmi_amd.init(0)
+    if args.forms:
+        return forms(args)
     nbytes = args.mib * MIB
     P = 8
 
@@ -107,14 +198,7 @@ def main():
                       "ratio_to_f32": round(statistics.median(ratios), 4),
                       "f32_spread": round((max(f32) - min(f32)) / statistics.median(f32), 4),
                       "timing": "two HIP events around back-to-back launches on the library stream"})
-    out = open(args.out, "a") if args.out else None
-    for line in lines:
-        s = json.dumps(line)
-        print(s, flush=True)
-        if out:
-            out.write(s + "\n")
-    if out:
-        out.close()
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":
