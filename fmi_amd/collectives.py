@@ -30,7 +30,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from . import _lib  # noqa: E402
-from .device import Alg, DType, Op  # noqa: E402
+from .device import Alg, DType, Op, acc_dtype  # noqa: E402
 
 _TORCH_DTYPE = {torch.float32: DType.F32, torch.float64: DType.F64, torch.int32: DType.I32, torch.int64: DType.I64,
                 torch.int8: DType.I8, torch.uint8: DType.U8, torch.int16: DType.I16, torch.float16: DType.F16,
@@ -68,10 +68,12 @@ class HipEngine:
         _lib.call("fmi_dev_reduce_pair", int(op), int(_dtype(inout)), inout.data_ptr(), src.data_ptr(),
                   inout.numel(), self._stream())
 
-    def reduce_tree(self, op: Op, alg: Alg, out: torch.Tensor, ins: Sequence[torch.Tensor], rank: int = 0) -> None:
+    def reduce_tree(self, op: Op, alg: Alg, out: torch.Tensor, ins: Sequence[torch.Tensor], rank: int = 0,
+                    accumulate_f32: bool = False) -> None:
         import ctypes
+        dtype = acc_dtype(_dtype(out), accumulate_f32)  # float16 / bfloat16 tensors only (FMI_ACC_F32)
         ptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
-        _lib.call("fmi_dev_reduce_tree", int(op), int(_dtype(out)), int(alg), out.data_ptr(), ptrs, len(ins), rank,
+        _lib.call("fmi_dev_reduce_tree", int(op), dtype, int(alg), out.data_ptr(), ptrs, len(ins), rank,
                   out.numel(), self._stream())
 
     def fill_synthetic(self, t: torch.Tensor, seed: int, peer: int) -> None:
@@ -86,9 +88,16 @@ class ShardedAllreduce:
     (src/comm/PeerToPeer.cpp:103,119) the first local bucket is overwritten with the partial result.
     """
 
-    def __init__(self, group=None, path: str = "tree", engine=None, force_exchange: bool = False):
+    def __init__(self, group=None, path: str = "tree", engine=None, force_exchange: bool = False,
+                 accumulate_f32: bool = False):
+        """accumulate_f32 (float16 / bfloat16 buckets, path "tree"): every P-way kernel keeps its values in f32 and
+        rounds what it stores once (FMI_ACC_F32); RCCL's reduction has its own order and rounding."""
         if path not in ("tree", "rccl"):
             raise ValueError("path must be 'tree' or 'rccl'")
+        if accumulate_f32 and path == "rccl":
+            raise ValueError("accumulate_f32 needs path 'tree': RCCL's reduction has its own order and rounding")
+        self.accumulate_f32 = bool(accumulate_f32)
+        self._acc = {"accumulate_f32": True} if accumulate_f32 else {}  # engines without the keyword keep working
         self.group = group if group is not None else dist.group.WORLD
         self.world = dist.get_world_size(self.group)
         self.rank = dist.get_rank(self.group)
@@ -127,7 +136,7 @@ class ShardedAllreduce:
         if L == 2:  # local round 0 of recursive doubling: pairs (2g, 2g+1)
             self.engine.reduce_pair(op, x, buckets[1])
         elif L > 2:  # local rounds 0..k-1: the 2^k-peer allreduce program over this GPU's peers
-            self.engine.reduce_tree(op, Alg.ALLREDUCE, x, buckets, rank=0)
+            self.engine.reduce_tree(op, Alg.ALLREDUCE, x, buckets, rank=0, **self._acc)
         N = self.world
         if N == 1 and not self.force_exchange:
             out.copy_(x)
@@ -151,13 +160,13 @@ class ShardedAllreduce:
                 # all-to-all (instead of the all-gather) delivers rank r's versions (same volume)
                 pers = self._buf("per_rank", padded, x)
                 for r in range(N):
-                    self.engine.reduce_tree(op, Alg.ALLREDUCE, pers[r * shard:(r + 1) * shard], parts, rank=r)
+                    self.engine.reduce_tree(op, Alg.ALLREDUCE, pers[r * shard:(r + 1) * shard], parts, rank=r, **self._acc)
                 gathered = out if padded == n else self._buf("pad_out", padded, x)
                 dist.all_to_all_single(gathered, pers, group=self.group)
                 if gathered is not out:
                     out.copy_(gathered[:n])
                 return out
-            self.engine.reduce_tree(op, Alg.ALLREDUCE, red, parts, rank=0)
+            self.engine.reduce_tree(op, Alg.ALLREDUCE, red, parts, rank=0, **self._acc)
         else:
             dist.reduce_scatter_tensor(red, src, op=_REDUCE_OP[op], group=self.group)
         gathered = out if padded == n else self._buf("pad_out", padded, x)

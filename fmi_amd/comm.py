@@ -18,7 +18,7 @@ import numpy as np
 
 from ._lib import Timeout  # noqa: F401 - FMI_ERR_TIMEOUT, the reference's FMI::Utils::Timeout
 
-from .device import Alg, Bucket, Op, _sptr, dtype_of, itemsize_of
+from .device import Alg, Bucket, Op, _sptr, acc_dtype, dtype_of, itemsize_of
 
 ID_BYTES = 128
 
@@ -114,10 +114,14 @@ class Comm:
         return float(ms.value), int(k.value)
 
     def allreduce(self, op: Op, send: Bucket, recv: Bucket, ordered: bool = False, path: Path = Path.TREE,
-                  stream=None) -> None:
+                  stream=None, accumulate_f32: bool = False) -> None:
+        """accumulate_f32 (F16 / BF16 buckets, here and in allreduce_host / reduce / scan): every rank's shard is
+        reduced on f32 values and rounded to the storage type once (FMI_ACC_F32); the wire stays 16-bit. Every rank
+        passes the same value. Path.RCCL has its own order and rounding and refuses it."""
         alg = Alg.REDUCE_LTR if ordered else Alg.ALLREDUCE
-        _lib.call("fmi_comm_allreduce", self.handle, int(op), int(send.dtype), int(alg), int(path), _p(send), _p(recv),
-                  send.n, _sptr(stream))
+        arg = acc_dtype(send.dtype, accumulate_f32)
+        _lib.call("fmi_comm_allreduce", self.handle, int(op), arg, int(alg), int(path), _p(send), _p(recv), send.n,
+                  _sptr(stream))
 
     def window(self, n: int, dtype) -> Bucket:
         """A symmetric window bucket for Path.DIRECT (collective: every rank, same n and dtype). Release it
@@ -132,30 +136,34 @@ class Comm:
         b.ptr = 0
 
     def allreduce_host(self, op: Op, send: np.ndarray, recv: np.ndarray, ordered: bool = False,
-                       path: Path = Path.TREE, chunk: int = 0) -> None:
+                       path: Path = Path.TREE, chunk: int = 0, accumulate_f32: bool = False, dtype=None) -> None:
         """Allreduce of HOST arrays (channel recv buffers, config C5), streamed through the GPU in
         `chunk`-element pieces (0 = FMI_TUNE_HOST_CHUNK). Page-locked arrays (PinnedArray.array) take the
-        DMA path. Blocking: `recv` holds the result on return."""
+        DMA path. Blocking: `recv` holds the result on return. `dtype`: the element type where the arrays carry raw
+        bits (DType.BF16 over np.uint16); None = the arrays' own."""
         if send.dtype != recv.dtype or send.size != recv.size:
             raise ValueError("allreduce_host: arrays must share dtype and size")
         if not (send.flags.c_contiguous and recv.flags.c_contiguous):
             raise ValueError("allreduce_host: arrays must be contiguous")
         alg = Alg.REDUCE_LTR if ordered else Alg.ALLREDUCE
-        _lib.call("fmi_comm_allreduce_host", self.handle, int(op), int(dtype_of(send)), int(alg), int(path),
+        arg = acc_dtype(dtype_of(send) if dtype is None else dtype, accumulate_f32)
+        _lib.call("fmi_comm_allreduce_host", self.handle, int(op), arg, int(alg), int(path),
                   send.ctypes.data, recv.ctypes.data, send.size, int(chunk))
 
     def reduce(self, op: Op, send: Bucket, recv: Optional[Bucket], root: int, ordered: bool = False,
-               stream=None, sendbuf_partials: bool = False) -> None:
+               stream=None, sendbuf_partials: bool = False, accumulate_f32: bool = False) -> None:
         """sendbuf_partials=True: `send` ends as the reference leaves peer `rank`'s sendbuf (the partial it
         forwarded up the binomial tree, reference src/comm/PeerToPeer.cpp:72) — fmi_comm_reduce_sendbuf."""
         alg = Alg.REDUCE_LTR if ordered else Alg.REDUCE
         fn = "fmi_comm_reduce_sendbuf" if sendbuf_partials else "fmi_comm_reduce"
-        _lib.call(fn, self.handle, int(op), int(send.dtype), int(alg), _p(send), _p(recv), send.n, root, _sptr(stream))
+        arg = acc_dtype(send.dtype, accumulate_f32)
+        _lib.call(fn, self.handle, int(op), arg, int(alg), _p(send), _p(recv), send.n, root, _sptr(stream))
 
-    def scan(self, op: Op, send: Bucket, recv: Bucket, ordered: bool = False, stream=None) -> None:
+    def scan(self, op: Op, send: Bucket, recv: Bucket, ordered: bool = False, stream=None,
+             accumulate_f32: bool = False) -> None:
         alg = Alg.SCAN_LTR if ordered else Alg.SCAN
-        _lib.call("fmi_comm_scan", self.handle, int(op), int(send.dtype), int(alg), _p(send), _p(recv), send.n,
-                  _sptr(stream))
+        arg = acc_dtype(send.dtype, accumulate_f32)
+        _lib.call("fmi_comm_scan", self.handle, int(op), arg, int(alg), _p(send), _p(recv), send.n, _sptr(stream))
 
     def bcast(self, buf: Bucket, root: int, stream=None) -> None:
         _lib.call("fmi_comm_bcast", self.handle, _p(buf), buf.nbytes, root, _sptr(stream))

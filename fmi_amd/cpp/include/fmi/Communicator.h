@@ -163,6 +163,17 @@ public:
     //! Where the last built-in combine of host buckets ran (tests, diagnostics): true = the GPU.
     bool last_host_combine_on_device() const { return last_on_device_->load(); }
 
+    //! The dtype argument a built-in Function's combines carry in device_op: A's fmi_dtype_t, with FMI_ACC_F32 for
+    //! Utils::Accumulate::f32 on Dev::half / Dev::bfloat16 elements; any other element type with it throws.
+    template <typename A, typename T>
+    static int device_dtype(const Utils::Function<T>& f) {
+        if (f.accumulate() != Utils::Accumulate::f32) return Dev::dtype_of<A>();
+        if constexpr (std::is_same_v<A, Dev::half> || std::is_same_v<A, Dev::bfloat16>)
+            return Dev::dtype_of<A>() | FMI_ACC_F32;
+        else
+            throw std::runtime_error("Accumulate::f32 needs Dev::half or Dev::bfloat16 elements");
+    }
+
     Utils::peer_num get_peer_id() const { return peer_id; }
     Utils::peer_num get_num_peers() const { return num_peers; }
 
@@ -201,7 +212,7 @@ private:
         if constexpr (Dev::device_type<A>) {
             if (op != Utils::Op::none) {
                 const std::size_t count = size_in_bytes / sizeof(A);
-                const device_op dop{static_cast<int>(op), Dev::dtype_of<A>(), count};
+                const device_op dop{static_cast<int>(op), device_dtype<A>(f), count};
                 if (offload_host_) {
                     // per combine: the GPU where it pays, else the host loop (the same op, so the same bits)
                     auto part = [dop, op, policy = policy, always = offload_always_, last = last_on_device_](
@@ -253,7 +264,7 @@ private:
     raw_function convert_to_raw_function(Utils::Function<Dev::Bucket<A>> f, std::size_t size_in_bytes) {
         if (f.builtin() == Utils::Op::none)
             throw std::runtime_error("device buckets need a built-in reduction op (Function<T>(Utils::Op::...))");
-        const device_op dop{static_cast<int>(f.builtin()), Dev::dtype_of<A>(), size_in_bytes / sizeof(A)};
+        const device_op dop{static_cast<int>(f.builtin()), device_dtype<A>(f), size_in_bytes / sizeof(A)};
         return raw_function{[dop](char* a, char* b) {
                                 Dev::check(fmi_dev_reduce_pair(dop.op, dop.dtype, a, b, dop.count, nullptr),
                                            "fmi_dev_reduce_pair");

@@ -30,6 +30,14 @@ namespace FMI::Utils {
 // Built-in reduction ops; numeric values are the C-ABI's fmi_op_t.
 enum class Op : int { none = -1, sum = FMI_OP_SUM, prod = FMI_OP_PROD, max = FMI_OP_MAX, min = FMI_OP_MIN };
 
+// What a P-way collective on Dev::half / Dev::bfloat16 elements keeps its running values in: `storage` rounds to the
+// 16-bit type after every combine (the reference's std::plus<__bf16>), `f32` keeps the program's values in f32 and
+// rounds every stored output once (fmi_dev.h, FMI_ACC_F32). It changes results only on channels that run whole
+// collectives through fmi_comm_* (Comm::Rccl). Channels built on pairwise combines (Loopback, LocalSocket,
+// PeerToPeer) round after every combine whatever it says: one combine is one rounding. With any other element
+// type, Accumulate::f32 makes the Communicator throw std::runtime_error.
+enum class Accumulate : int { storage = 0, f32 = 1 };
+
 namespace detail {
 
 // Integers wrap: computed in an unsigned type at least as wide as unsigned int (so sub-int types do not
@@ -95,12 +103,16 @@ public:
         if (op == Op::none) throw std::runtime_error("Function: Op::none is not a built-in op");
     }
 
+    // Built-in op with the accumulation type of P-way collectives (above).
+    Function(Op op, Accumulate acc) : Function(op) { acc_ = acc; }
+
     T operator()(T a, T b) const {
         if (!f_) throw std::runtime_error("Function: device-bucket functions have no host evaluation");
         return f_(std::move(a), std::move(b));
     }
 
     Op builtin() const { return op_; }
+    Accumulate accumulate() const { return acc_; }
 
     //! User provided information about commutativity
     bool commutative;
@@ -110,6 +122,7 @@ public:
 private:
     std::function<T(T, T)> f_;
     Op op_ = Op::none;
+    Accumulate acc_ = Accumulate::storage;
 };
 
 }  // namespace FMI::Utils

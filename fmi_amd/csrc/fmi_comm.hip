@@ -1446,10 +1446,15 @@ int aborted_error() {
     return fail(FMI_ERR_COMM, "communicator was aborted (a timeout or a transport error); destroy it");
 }
 
-int check_common(fmi_comm_t comm, int op, int dtype) {
+// *kd: the dtype argument in canonical form, what the shard step hands to fmi_dev_reduce_tree / fmi_dev_scan_peers /
+// reduce_partials (FMI_ACC_F32 validated, dropped for max / min); *dtype: its storage dtype, for everything else
+// (sizes, the wire, order_sensitive).
+int check_common(fmi_comm_t comm, int op, int* dtype, int* kd) {
     if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
     if (op < FMI_OP_SUM || op > FMI_OP_MIN) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
-    if (dtype_size(dtype) == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(dtype));
+    FMI_COMM_RC(canonical_dtype(op, *dtype, true, 0, kd));
+    *dtype = storage_dtype(*kd);
+    if (dtype_size(*dtype) == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(*dtype));
     if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
     if (static_cast<Comm*>(comm)->t->aborted()) return aborted_error();
     return FMI_OK;
@@ -1507,7 +1512,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 // the N reduced shards straight from the peers' windows. Two stream-ordered barriers: before the reduce
 // (every bucket written) and before the gather (every shard reduced). The next call's first barrier keeps
 // a rank from overwriting its reduced shard while a peer still gathers it.
-int allreduce_direct(Comm* c, const Window& w, size_t off, int op, int dtype, int alg, void* recv, size_t n,
+int allreduce_direct(Comm* c, const Window& w, size_t off, int op, int dtype, int kd, int alg, void* recv, size_t n,
                      hipStream_t s) {
     const int N = c->t->n();
     const int k = c->t->rank();
@@ -1534,7 +1539,7 @@ int allreduce_direct(Comm* c, const Window& w, size_t off, int op, int dtype, in
         for (int j = 0; j < N; ++j) ins[j] = w.peers[j] + off + lo * esz;
         char* out = w.peers[k] + w.bytes + off + lo * esz;
         FMI_COMM_RC(c->timing.begin(s));
-        FMI_COMM_RC(fmi_dev_reduce_tree(op, dtype, alg, out, ins.data(), N, 0, len, s));
+        FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, out, ins.data(), N, 0, len, s));
         FMI_COMM_RC(c->timing.end(s));
     }
     FMI_COMM_RC(c->t->barrier_async(s));
@@ -1559,7 +1564,7 @@ int allreduce_direct(Comm* c, const Window& w, size_t off, int op, int dtype, in
 // of a sub-range (element-wise, so the bits are those of the whole-bucket call), with chunk c's all-gather
 // on a second stream and communicator while chunk c + 1's all-to-all and kernel run on `s`. Two buffer slots;
 // events order their reuse: the kernel of chunk c + 2 waits until chunk c's gather has read its shard.
-int allreduce_tree_pipelined(Comm* c, int op, int dtype, int alg, const void* send, void* recv, size_t n,
+int allreduce_tree_pipelined(Comm* c, int op, int dtype, int kd, int alg, const void* send, void* recv, size_t n,
                              hipStream_t s, size_t K) {
     const int N = c->t->n();
     const size_t esz = dtype_size(dtype);
@@ -1595,7 +1600,7 @@ int allreduce_tree_pipelined(Comm* c, int op, int dtype, int alg, const void* se
         std::vector<const void*> parts(N);
         for (int r = 0; r < N; ++r) parts[r] = staging + r * shard * esz;
         FMI_COMM_RC(c->timing.begin(s));
-        FMI_COMM_RC(fmi_dev_reduce_tree(op, dtype, alg, red, parts.data(), N, 0, shard, s));
+        FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, shard, s));
         FMI_COMM_RC(c->timing.end(s));
         FMI_COMM_HIP(hipEventRecord(p.reduced[j], s));
         FMI_COMM_HIP(hipStreamWaitEvent(p.gs, p.reduced[j], 0));
@@ -1614,8 +1619,9 @@ int allreduce_tree_pipelined(Comm* c, int op, int dtype, int alg, const void* se
     return FMI_OK;
 }
 
-// The sharded allreduce of one device bucket on stream s (caller holds c->mu; arguments validated).
-int allreduce_device(Comm* c, int op, int dtype, int alg, int path, const void* send, void* recv, size_t n,
+// The sharded allreduce of one device bucket on stream s (caller holds c->mu; arguments validated). dtype: the
+// storage dtype; kd: the shard step's dtype argument (check_common).
+int allreduce_device(Comm* c, int op, int dtype, int kd, int alg, int path, const void* send, void* recv, size_t n,
                      hipStream_t s) {
     const int N = c->t->n();
     const size_t esz = dtype_size(dtype);
@@ -1632,7 +1638,7 @@ int allreduce_device(Comm* c, int op, int dtype, int alg, int path, const void* 
         size_t off = 0;
         const Window* w = c->window_of(send, n * esz, &off);
         if (!w) return fail(FMI_ERR_INVALID, "path DIRECT: send must lie inside a window from fmi_comm_window_alloc");
-        if (!per_rank) return allreduce_direct(c, *w, off, op, dtype, alg, recv, n, s);
+        if (!per_rank) return allreduce_direct(c, *w, off, op, dtype, kd, alg, recv, n, s);
     }
     if (path == FMI_PATH_TREE && !per_rank) {
         const long long K = tune(FMI_TUNE_COMM_PIPELINE);
@@ -1641,7 +1647,7 @@ int allreduce_device(Comm* c, int op, int dtype, int alg, int path, const void* 
         if (K >= 2 && n * esz / static_cast<size_t>(K) >= (size_t(1) << 20) * static_cast<size_t>(N) &&
             !c->chunks.no_split) {
             const int rc = c->chunks.init(c->t.get(), s);
-            if (rc == FMI_OK) return allreduce_tree_pipelined(c, op, dtype, alg, send, recv, n, s, static_cast<size_t>(K));
+            if (rc == FMI_OK) return allreduce_tree_pipelined(c, op, dtype, kd, alg, send, recv, n, s, static_cast<size_t>(K));
             if (rc != FMI_ERR_UNSUPPORTED) return rc;
         }
     }
@@ -1659,7 +1665,7 @@ int allreduce_device(Comm* c, int op, int dtype, int alg, int path, const void* 
             std::vector<const void*> parts(N);
             for (int j = 0; j < N; ++j) parts[j] = staging + j * shard * esz;
             FMI_COMM_RC(c->timing.begin(s));
-            FMI_COMM_RC(fmi_dev_reduce_tree(op, dtype, alg, red, parts.data(), N, 0, len, s));
+            FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, len, s));
             FMI_COMM_RC(c->timing.end(s));
         }
         return c->t->all_gather_ragged(red, static_cast<char*>(recv), shard * esz, n * esz, s);
@@ -1694,7 +1700,7 @@ int allreduce_device(Comm* c, int op, int dtype, int alg, int path, const void* 
                 FMI_COMM_RC(launch_fused_allreduce_all_ranks(op, dtype, N, ptrs, shard, s));
             } else {
                 for (int r = 0; r < N; ++r)
-                    FMI_COMM_RC(fmi_dev_reduce_tree(op, dtype, alg, red + r * shard * esz, parts.data(), N, r, shard, s));
+                    FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red + r * shard * esz, parts.data(), N, r, shard, s));
             }
             FMI_COMM_RC(c->timing.end(s));
             if (padded == n) return c->t->all_to_all(red, static_cast<char*>(recv), shard * esz, s);
@@ -1705,7 +1711,7 @@ int allreduce_device(Comm* c, int op, int dtype, int alg, int path, const void* 
             return FMI_OK;
         }
         FMI_COMM_RC(c->timing.begin(s));
-        FMI_COMM_RC(fmi_dev_reduce_tree(op, dtype, alg, red, parts.data(), N, 0, shard, s));
+        FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, shard, s));
         FMI_COMM_RC(c->timing.end(s));
     } else {
         FMI_COMM_RC(c->t->reduce_scatter(op, dtype, src, red, shard, s));
@@ -1943,13 +1949,17 @@ int fmi_comm_timing_read(fmi_comm_t comm, float* total_ms, int* launches) {
 
 static int comm_allreduce_impl(fmi_comm_t comm, int op, int dtype, int alg, int path, const void* send, void* recv, size_t n,
                        fmi_stream_t stream) {
-    FMI_COMM_RC(check_common(comm, op, dtype));
+    int kd = 0;  // the shard step's dtype argument (check_common)
+    FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
     FMI_COMM_RC(check_allreduce_args(alg, path));
+    if (path == FMI_PATH_RCCL && accumulates_f32(kd))
+        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: FMI_ACC_F32 needs path TREE or DIRECT (RCCL's reduction has its own order "
+                                         "and rounding)");
     if (n == 0) return FMI_OK;
     if (!send || !recv) return fail(FMI_ERR_INVALID, "null bucket");
     Comm* c = static_cast<Comm*>(comm);
     std::lock_guard<std::mutex> lk(c->mu);
-    return allreduce_device(c, op, dtype, alg, path, send, recv, n, resolve_stream(stream));
+    return allreduce_device(c, op, dtype, kd, alg, path, send, recv, n, resolve_stream(stream));
 }
 
 // Three-stage pipeline over HostPipe::depth() chunk slots: while chunk k is allreduced on pipe.cs, chunk k+1 loads on
@@ -1958,8 +1968,12 @@ static int comm_allreduce_impl(fmi_comm_t comm, int op, int dtype, int alg, int 
 // (reduced), an allreduce into slot j waits until the previous result in it has drained to the host.
 static int comm_allreduce_host_impl(fmi_comm_t comm, int op, int dtype, int alg, int path, const void* send, void* recv,
                             size_t n, size_t chunk) {
-    FMI_COMM_RC(check_common(comm, op, dtype));
+    int kd = 0;  // the shard step's dtype argument (check_common)
+    FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
     FMI_COMM_RC(check_allreduce_args(alg, path));
+    if (path == FMI_PATH_RCCL && accumulates_f32(kd))
+        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: FMI_ACC_F32 needs path TREE or DIRECT (RCCL's reduction has its own order "
+                                         "and rounding)");
     if (n == 0) return FMI_OK;
     if (!send || !recv) return fail(FMI_ERR_INVALID, "null bucket");
     Comm* c = static_cast<Comm*>(comm);
@@ -2004,7 +2018,7 @@ static int comm_allreduce_host_impl(fmi_comm_t comm, int op, int dtype, int alg,
             FMI_COMM_HIP(hipStreamWaitEvent(p.cs, p.drained[j], 0));
             FMI_COMM_RC(c->t->wait_event(p.drained[j], p.d2h, "fmi_comm_allreduce_host (a chunk's exchange)"));
         }
-        FMI_COMM_RC(allreduce_device(c, op, dtype, alg, path, in[j], out[j], span(k), p.cs));
+        FMI_COMM_RC(allreduce_device(c, op, dtype, kd, alg, path, in[j], out[j], span(k), p.cs));
         FMI_COMM_HIP(hipEventRecord(p.reduced[j], p.cs));
         FMI_COMM_HIP(hipStreamWaitEvent(p.d2h, p.reduced[j], 0));
         FMI_COMM_HIP(hipMemcpyAsync(dst + k * chunk * esz, out[j], span(k) * esz, hipMemcpyDefault, p.d2h));
@@ -2017,7 +2031,8 @@ static int comm_allreduce_host_impl(fmi_comm_t comm, int op, int dtype, int alg,
 
 static int comm_reduce_impl(fmi_comm_t comm, int op, int dtype, int alg, const void* send, void* recv, size_t n, int root,
                     fmi_stream_t stream) {
-    FMI_COMM_RC(check_common(comm, op, dtype));
+    int kd = 0;  // the shard step's dtype argument (check_common)
+    FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
     if (alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
         return fail(FMI_ERR_INVALID, "reduce: alg must be REDUCE or REDUCE_LTR");
     Comm* c = static_cast<Comm*>(comm);
@@ -2044,13 +2059,13 @@ static int comm_reduce_impl(fmi_comm_t comm, int op, int dtype, int alg, const v
     if (padded != n && c->t->ragged()) {  // short last shards at their own length: no padded copies
         FMI_COMM_RC(c->t->all_to_all_ragged(static_cast<const char*>(send), staging, shard * esz, n * esz, s));
         const size_t len = Transport::span(c->t->rank(), shard, n);
-        FMI_COMM_RC(fmi_dev_reduce_tree(op, dtype, alg, red, parts.data(), N, root, len, s));
+        FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, root, len, s));
         return c->t->gather_ragged(red, is_root ? static_cast<char*>(recv) : nullptr, shard * esz, n * esz, root, s);
     }
     const char* src = nullptr;
     FMI_COMM_RC(padded_source(c, n, padded, esz, send, s, &src));
     FMI_COMM_RC(c->t->all_to_all(src, staging, shard * esz, s));
-    FMI_COMM_RC(fmi_dev_reduce_tree(op, dtype, alg, red, parts.data(), N, root, shard, s));
+    FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, root, shard, s));
     if (padded == n) return c->t->gather(red, is_root ? static_cast<char*>(recv) : nullptr, shard * esz, root, s);
     char* out = nullptr;
     FMI_COMM_RC(c->scratch(3, padded * esz, s, &out));
@@ -2067,7 +2082,8 @@ static int comm_reduce_impl(fmi_comm_t comm, int op, int dtype, int alg, const v
 static int comm_reduce_sendbuf_impl(fmi_comm_t comm, int op, int dtype, int alg, void* send, void* recv, size_t n, int root,
                             fmi_stream_t stream) {
     if (alg == FMI_ALG_REDUCE_LTR) return comm_reduce_impl(comm, op, dtype, alg, send, recv, n, root, stream);
-    FMI_COMM_RC(check_common(comm, op, dtype));
+    int kd = 0;  // the shard step's dtype argument (check_common)
+    FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
     if (alg != FMI_ALG_REDUCE) return fail(FMI_ERR_INVALID, "reduce: alg must be REDUCE or REDUCE_LTR");
     Comm* c = static_cast<Comm*>(comm);
     const int N = c->t->n();
@@ -2103,7 +2119,7 @@ static int comm_reduce_sendbuf_impl(fmi_comm_t comm, int op, int dtype, int alg,
             outs[t] = partial + real * shard * esz;
         }
         const size_t len = ragged ? Transport::span(c->t->rank(), shard, n) : shard;
-        FMI_COMM_RC(reduce_partials(op, dtype, outs.data(), ins.data(), N, len, s));
+        FMI_COMM_RC(reduce_partials(op, kd, outs.data(), ins.data(), N, len, s));
         if (ragged) {
             FMI_COMM_RC(c->t->all_to_all_back_ragged(partial, static_cast<char*>(send), shard * esz, n * esz, s));
         } else if (padded == n) {
@@ -2121,7 +2137,8 @@ static int comm_reduce_sendbuf_impl(fmi_comm_t comm, int op, int dtype, int alg,
 
 static int comm_scan_impl(fmi_comm_t comm, int op, int dtype, int alg, const void* send, void* recv, size_t n,
                   fmi_stream_t stream) {
-    FMI_COMM_RC(check_common(comm, op, dtype));
+    int kd = 0;  // the shard step's dtype argument (check_common)
+    FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
     if (alg != FMI_ALG_SCAN && alg != FMI_ALG_SCAN_LTR) return fail(FMI_ERR_INVALID, "scan: alg must be SCAN or SCAN_LTR");
     if (n == 0) return FMI_OK;
     if (!send || !recv) return fail(FMI_ERR_INVALID, "null bucket");
@@ -2149,13 +2166,13 @@ static int comm_scan_impl(fmi_comm_t comm, int op, int dtype, int alg, const voi
     if (padded != n && c->t->ragged()) {  // short last shards at their own length: no padded copies
         FMI_COMM_RC(c->t->all_to_all_ragged(static_cast<const char*>(send), staging, shard * esz, n * esz, s));
         const size_t len = Transport::span(c->t->rank(), shard, n);
-        FMI_COMM_RC(fmi_dev_scan_peers(op, dtype, alg, outs.data(), ins.data(), N, len, s));
+        FMI_COMM_RC(fmi_dev_scan_peers(op, kd, alg, outs.data(), ins.data(), N, len, s));
         return c->t->all_to_all_back_ragged(prefix, static_cast<char*>(recv), shard * esz, n * esz, s);
     }
     const char* src = nullptr;
     FMI_COMM_RC(padded_source(c, n, padded, esz, send, s, &src));
     FMI_COMM_RC(c->t->all_to_all(src, staging, shard * esz, s));
-    FMI_COMM_RC(fmi_dev_scan_peers(op, dtype, alg, outs.data(), ins.data(), N, shard, s));
+    FMI_COMM_RC(fmi_dev_scan_peers(op, kd, alg, outs.data(), ins.data(), N, shard, s));
     // rank k gathers its prefix shard j from rank j: an all-to-all back
     if (padded == n) return c->t->all_to_all(prefix, static_cast<char*>(recv), shard * esz, s);
     char* out = nullptr;

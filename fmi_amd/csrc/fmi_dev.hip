@@ -284,14 +284,19 @@ int launch_combine(int op, int dtype, void* out, const void* a, const void* b, s
 // Scratch arena for P-way temporaries (caller holds g_mu). Stream s waits until the previous user's work
 // has drained; the caller records g_state.arena_free on s after its last launch touching the arena.
 // ----------------------------------------------------------------------------------------------------
-int arena_acquire(size_t need, hipStream_t s) {
-    // The arena is ordered by an event recorded outside any graph: a captured call would record arena_free
-    // inside the graph, and its replays would write the arena unordered against later direct calls.
+// Temporaries of the library's own are ordered by an event recorded outside any graph: a captured call would record
+// the event inside the graph, and its replays would write them unordered against later direct calls.
+int refuse_capture(hipStream_t s, const char* needs) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     FMI_HIP_TRY(hipStreamIsCapturing(s, &cap));
     if (cap != hipStreamCaptureStatusNone)
-        return fail(FMI_ERR_UNSUPPORTED, "this call needs the library's scratch arena (unaligned or 8/16-bit buckets, "
-                                         "or a P-way program beyond the fused kernels) and cannot be captured in a graph");
+        return fail(FMI_ERR_UNSUPPORTED, std::string("this call needs ") + needs + " and cannot be captured in a graph");
+    return FMI_OK;
+}
+
+int arena_acquire(size_t need, hipStream_t s) {
+    FMI_RC_TRY(refuse_capture(s, "the library's scratch arena (unaligned or 8/16-bit buckets, or a P-way program beyond "
+                                 "the fused kernels)"));
     if (!g_state.arena_free) FMI_HIP_TRY(hipEventCreateWithFlags(&g_state.arena_free, hipEventDisableTiming));
     if (g_state.arena_bytes < need) {
         FMI_HIP_TRY(hipEventSynchronize(g_state.arena_free));  // previous users have drained
@@ -801,10 +806,102 @@ std::string expr_of(const sched::HostProgram& prog, int v) {
     return e;
 }
 
+// ----------------------------------------------------------------------------------------------------
+// FMI_ACC_F32 beyond the fused acc32 kernels (P > 16, or a bucket that is not 16-B aligned): widen every input into
+// an f32 temporary, run the library's own FMI_F32 program on the temporaries (every family f32 has, unchanged), narrow
+// every stored output: out = narrow(F32_program(widen(x))) by construction. The inner program may take the scratch
+// arena under g_mu and reallocate it, so the temporaries live in an allocation of their own (g_acc, ordered by its
+// own event the way arena_acquire orders the arena, and like it not capturable) under a lock of their own: g_acc_mu
+// is held while the call's launches are enqueued, g_mu is only ever taken inside it, never around it.
+// ----------------------------------------------------------------------------------------------------
+struct AccTemps {
+    void* buf = nullptr;
+    size_t bytes = 0;
+    hipEvent_t free = nullptr;  // the work that last used buf has drained
+};
+std::mutex g_acc_mu;
+AccTemps g_acc;
+
+int acc_acquire(size_t need, hipStream_t s) {  // caller holds g_acc_mu
+    FMI_RC_TRY(refuse_capture(s, "f32 temporaries (FMI_ACC_F32 beyond 16 peers or on unaligned buckets)"));
+    if (!g_acc.free) FMI_HIP_TRY(hipEventCreateWithFlags(&g_acc.free, hipEventDisableTiming));
+    if (g_acc.bytes < need) {
+        FMI_HIP_TRY(hipEventSynchronize(g_acc.free));  // previous users have drained
+        if (g_acc.buf) FMI_HIP_TRY(hipFree(g_acc.buf));
+        g_acc.buf = nullptr;
+        g_acc.bytes = 0;
+        const hipError_t e = hipMalloc(&g_acc.buf, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();  // not left for the next launch's error check to find
+            return fail(FMI_ERR_ALLOC, "hipMalloc(" + std::to_string(need) + ") for FMI_ACC_F32's f32 temporaries: " +
+                                           hipGetErrorString(e));
+        }
+        g_acc.bytes = need;
+    }
+    FMI_HIP_TRY(hipStreamWaitEvent(s, g_acc.free, 0));
+    return FMI_OK;
+}
+
+void acc_release() {  // fmi_dev_finalize (holding g_acc_mu), after the device has drained
+    if (g_acc.buf) (void)hipFree(g_acc.buf);
+    if (g_acc.free) (void)hipEventDestroy(g_acc.free);
+    g_acc = AccTemps{};
+}
+
+// `inner(f32_outs, f32_ins)` runs the FMI_F32 program; f32 output k is temporary `out_slot[k]` (an input's own
+// temporary where the program may run in place, a further one otherwise), `ntemps` temporaries in all.
+template <class Inner>
+int acc32_fallback(int dtype, void* const* outs, const int* out_slot, int nouts, const void* const* ins, int P,
+                   int ntemps, size_t n, hipStream_t s, Inner&& inner) {
+    const size_t stride = arena_stride(n, sizeof(float));
+    size_t need = 0;
+    if (__builtin_mul_overflow(stride, static_cast<size_t>(ntemps), &need))
+        return fail(FMI_ERR_ALLOC, "FMI_ACC_F32's f32 temporaries: size overflows");
+    std::lock_guard<std::mutex> lk(g_acc_mu);
+    FMI_RC_TRY(acc_acquire(need, s));
+    auto temp = [&](int k) { return reinterpret_cast<float*>(static_cast<char*>(g_acc.buf) + stride * static_cast<size_t>(k)); };
+    std::vector<const void*> fin(P);
+    std::vector<void*> fout(nouts);
+    int rc = FMI_OK;
+    for (int p = 0; p < P && rc == FMI_OK; ++p) {
+        fin[p] = temp(p);
+        rc = launch_widen_f32(dtype, temp(p), ins[p], n, s);
+    }
+    for (int k = 0; k < nouts; ++k) fout[k] = temp(out_slot[k]);
+    if (rc == FMI_OK) rc = inner(fout.data(), fin.data());
+    for (int k = 0; k < nouts && rc == FMI_OK; ++k) rc = launch_narrow_f32(dtype, outs[k], temp(out_slot[k]), n, s);
+    FMI_HIP_TRY(hipEventRecord(g_acc.free, s));
+    return rc;
+}
+
+bool all_aligned16(const void* const* a, void* const* b, int P) {
+    bool ok = true;
+    for (int p = 0; p < P; ++p) ok = ok && aligned16(a[p]) && (!b || aligned16(b[p]));
+    return ok;
+}
+
 }  // namespace
 
-int reduce_partials(int op, int dtype, void* const* outs, const void* const* ins, int P, size_t n, hipStream_t s) {
+int reduce_partials(int op, int dtype_arg, void* const* outs, const void* const* ins, int P, size_t n, hipStream_t s) {
     if (n == 0) return FMI_OK;
+    int dtype = 0;
+    FMI_RC_TRY(canonical_dtype(op, dtype_arg, true, P, &dtype));
+    if (accumulates_f32(dtype)) {
+        const int st = storage_dtype(dtype);
+        if (P <= sched::kMaxFusedPeers && all_aligned16(ins, outs, P)) {
+            PeerPtrs ptrs{};
+            for (int p = 0; p < P; ++p) {
+                ptrs.in[p] = ins[p];
+                ptrs.out[p] = outs[p];
+            }
+            return launch_fused_reduce_partials(op, dtype, P, ptrs, n, s);
+        }
+        std::vector<int> slot(P);
+        for (int p = 0; p < P; ++p) slot[p] = p;  // in place: partial t overwrites input t's temporary
+        return acc32_fallback(st, outs, slot.data(), P, ins, P, P, n, s, [&](void* const* fo, const void* const* fi) {
+            return reduce_partials(op, FMI_F32, fo, fi, P, n, s);
+        });
+    }
     bool aligned = true;
     for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]) && aligned16(outs[p]);
     if (P >= 2 && P <= sched::kMaxFusedPeers && aligned && fused_covers(op, dtype, sched::kReducePartials, P)) {
@@ -928,6 +1025,7 @@ int fmi_dev_init(int device) {
 }
 
 int fmi_dev_finalize(void) {
+    std::lock_guard<std::mutex> acc_lk(g_acc_mu);  // before g_mu: the order an FMI_ACC_F32 fallback call takes them in
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_state.device < 0) return FMI_OK;
     (void)hipSetDevice(g_state.device);
@@ -941,6 +1039,7 @@ int fmi_dev_finalize(void) {
         pipes().all.clear();
         pipes().idle.clear();
     }
+    acc_release();
     if (g_state.arena) (void)hipFree(g_state.arena);
     if (g_state.arena_free) (void)hipEventDestroy(g_state.arena_free);
     if (g_state.stream) (void)hipStreamDestroy(g_state.stream);
@@ -1253,11 +1352,13 @@ int fmi_graph_destroy(fmi_graph_t graph) {
 
 // ---- hot path ----------------------------------------------------------------------------------------
 int fmi_dev_reduce_pair(int op, int dtype, void* inout, const void* in, size_t n, fmi_stream_t stream) {
+    if (int rc = canonical_dtype(op, dtype, false, 2, &dtype)) return rc;  // one combine is one rounding: FMI_ACC_F32 dropped
     if (int rc = require_device()) return rc;
     return launch_combine(op, dtype, inout, inout, in, n, resolve(stream));
 }
 
 int fmi_dev_reduce_pair_batch(int op, int dtype, const fmi_pair_desc_t* descs, int count, fmi_stream_t stream) {
+    if (int rc = canonical_dtype(op, dtype, false, 2, &dtype)) return rc;
     if (int rc = require_device()) return rc;
     if (op < FMI_OP_SUM || op > FMI_OP_MIN) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
     const size_t esz = dtype_size(dtype);
@@ -1321,12 +1422,17 @@ int fmi_dev_reduce_pair_batch(int op, int dtype, const fmi_pair_desc_t* descs, i
 }
 
 int fmi_dev_combine(int op, int dtype, void* out, const void* a, const void* b, size_t n, fmi_stream_t stream) {
+    if (int rc = canonical_dtype(op, dtype, false, 2, &dtype)) return rc;
     if (int rc = require_device()) return rc;
     return launch_combine(op, dtype, out, a, b, n, resolve(stream));
 }
 
-static int reduce_tree_impl(int op, int dtype, int alg, void* out, const void* const* ins, int P, int rank, size_t n,
+static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const void* const* ins, int P, int rank, size_t n,
                             fmi_stream_t stream) {
+    int dtype = 0;  // the storage dtype from here on; `acc`: the program's values are f32 (FMI_ACC_F32)
+    if (int rc = canonical_dtype(op, dtype_arg, true, P, &dtype)) return rc;
+    const bool acc = accumulates_f32(dtype);
+    dtype = storage_dtype(dtype);
     if (int rc = check_peer_args(op, dtype, P)) return rc;
     if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
         return fail(FMI_ERR_INVALID, "fmi_dev_reduce_tree: alg must be ALLREDUCE, REDUCE or REDUCE_LTR");
@@ -1343,7 +1449,16 @@ static int reduce_tree_impl(int op, int dtype, int alg, void* out, const void* c
     for (int t = 0; t < P; ++t) order[t] = ins[alg == FMI_ALG_REDUCE ? (t + rank) % P : t];
     bool aligned = aligned16(out);
     for (int p = 0; p < P; ++p) aligned = aligned && aligned16(order[p]);
-    if (P >= 2 && aligned && fused_covers(op, dtype, alg, P)) {
+    if (acc && (P > sched::kMaxFusedPeers || !aligned)) {
+        // the inner call applies the root's rotation itself: the temporaries keep the caller's order
+        const int slot = P;  // the result in a temporary of its own
+        void* outs[1] = {out};
+        return acc32_fallback(dtype, outs, &slot, 1, ins, P, P + 1, n, s, [&](void* const* fo, const void* const* fi) {
+            return reduce_tree_impl(op, FMI_F32, alg, fo[0], fi, P, rank, n, stream);
+        });
+    }
+    if (acc) dtype |= FMI_ACC_F32;  // launch_fused hands these to the acc32 units
+    if (P >= 2 && aligned && fused_covers(op, storage_dtype(dtype), alg, P)) {
         if (P > sched::max_fused_peers(alg)) return run_tree_blocked(op, dtype, alg, out, order.data(), P, rank, n, s);
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) ptrs.in[p] = order[p];
@@ -1361,8 +1476,12 @@ static int reduce_tree_impl(int op, int dtype, int alg, void* out, const void* c
     return run_program_stepwise(op, dtype, prog, outs, 1, &value, order.data(), n, s);
 }
 
-static int scan_peers_impl(int op, int dtype, int alg, void* const* outs, const void* const* ins, int P, size_t n,
+static int scan_peers_impl(int op, int dtype_arg, int alg, void* const* outs, const void* const* ins, int P, size_t n,
                            fmi_stream_t stream) {
+    int dtype = 0;  // as in reduce_tree_impl
+    if (int rc = canonical_dtype(op, dtype_arg, true, P, &dtype)) return rc;
+    const bool acc = accumulates_f32(dtype);
+    dtype = storage_dtype(dtype);
     if (int rc = check_peer_args(op, dtype, P)) return rc;
     if (alg != FMI_ALG_SCAN && alg != FMI_ALG_SCAN_LTR)
         return fail(FMI_ERR_INVALID, "fmi_dev_scan_peers: alg must be SCAN or SCAN_LTR");
@@ -1374,7 +1493,15 @@ static int scan_peers_impl(int op, int dtype, int alg, void* const* outs, const 
     hipStream_t s = resolve(stream);
     bool aligned = true;
     for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]) && aligned16(outs[p]);
-    if (P >= 2 && aligned && fused_covers(op, dtype, alg, P)) {
+    if (acc && (P > sched::kMaxFusedPeers || !aligned)) {
+        std::vector<int> slot(P);
+        for (int p = 0; p < P; ++p) slot[p] = p;  // in place: prefix p overwrites input p's temporary
+        return acc32_fallback(dtype, outs, slot.data(), P, ins, P, P, n, s, [&](void* const* fo, const void* const* fi) {
+            return scan_peers_impl(op, FMI_F32, alg, fo, fi, P, n, stream);
+        });
+    }
+    if (acc) dtype |= FMI_ACC_F32;  // launch_fused hands these to the acc32 units
+    if (P >= 2 && aligned && fused_covers(op, storage_dtype(dtype), alg, P)) {
         if (P > sched::max_fused_peers(alg)) return run_scan_blocked(op, dtype, alg, outs, ins, P, n, s);
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) {
@@ -1395,6 +1522,7 @@ static int scan_peers_impl(int op, int dtype, int alg, void* const* outs, const 
 // keeps a slot's staging from being overwritten before its previous D2H finished, while the other slot's
 // H2D overlaps this slot's kernel + D2H.
 int fmi_host_reduce_pair(int op, int dtype, void* inout, const void* in, size_t n) {
+    if (int rc = canonical_dtype(op, dtype, false, 2, &dtype)) return rc;
     if (op < FMI_OP_SUM || op > FMI_OP_MIN) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
     const size_t esz = dtype_size(dtype);
     if (esz == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(dtype));

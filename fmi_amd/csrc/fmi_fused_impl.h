@@ -43,6 +43,7 @@ template <int ALG, bool RANK_AWARE, int LO = 2, int HI = sched::kMaxFusedPeers, 
 int launch_fused(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s) {
     static_assert(2 <= LO && LO <= HI && HI <= sched::max_fused_peers(ALG), "fused peer range");
     if constexpr (TIER == kTierCore) {
+        if (accumulates_f32(dtype)) return launch_fused_acc32(ALG, op, dtype, P, ptrs, n, s);
         if (is_half_dtype(dtype)) return launch_fused_half(ALG, RANK_AWARE, op, dtype, P, ptrs, n, rank, s);
     }
     if (P < LO || P > HI)
@@ -55,6 +56,40 @@ int launch_fused(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int r
             fused_table<Op, T, ALG, order_sensitive, LO>(std::make_integer_sequence<int, HI - LO + 1>{});
         table[P - LO](ptrs, n, order_sensitive ? rank : 0, s);
         return check_launch("fused P-way kernel launch");
+    });
+}
+
+// FMI_ACC_F32: the same programs on f32 values over 16-bit float storage (the kernels at element Acc32<T>), sum
+// and prod, P = 2..16, one family per translation unit (fmi_fused_acc32_*.hip). dtype: the storage dtype.
+template <class Op, class T, int ALG, int P>
+void fused_acc32_one(const PeerPtrs& ptrs, size_t n, int, hipStream_t s) {
+    const size_t nvec = n / kVecLanes<T>;
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(grid_for(nvec, kFusedBlock), kFusedGridCap));
+    const size_t lds = fused_lds_bytes(P, kFusedBlock * 16);
+    if constexpr (sched::stores_all_outputs(ALG))
+        scan_kernel<Op, Acc32<T>, ALG, P><<<grid, kFusedBlock, lds, s>>>(ptrs, n, fused_policy(true, P));
+    else
+        tree_kernel<Op, Acc32<T>, ALG, P, false><<<grid, kFusedBlock, lds, s>>>(ptrs, n, 0, fused_policy(false, P));
+}
+
+template <class Op, class T, int ALG, int... I>
+constexpr std::array<FusedFn, sizeof...(I)> fused_acc32_table(std::integer_sequence<int, I...>) {
+    return {&fused_acc32_one<Op, T, ALG, I + 2>...};
+}
+
+template <int ALG>
+int launch_fused_acc32_family(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
+    if (P < 2 || P > sched::kMaxFusedPeers)
+        return fail(FMI_ERR_INVALID, "fused f32-accumulating kernel needs 2 <= P <= 16, got " + std::to_string(P));
+    return with_op_dtype<kTierHalf>(op, dtype, [&]<class Op, class T>() -> int {
+        if constexpr (std::is_same_v<Op, OpSum> || std::is_same_v<Op, OpProd>) {
+            static constexpr auto table =
+                fused_acc32_table<Op, T, ALG>(std::make_integer_sequence<int, sched::kMaxFusedPeers - 1>{});
+            table[P - 2](ptrs, n, 0, s);
+            return check_launch("fused f32-accumulating kernel launch");
+        } else {
+            return fail(FMI_ERR_INVALID, "f32 accumulation: max / min are selections and run the plain kernels");
+        }
     });
 }
 

@@ -48,6 +48,24 @@ inline bool is_core_dtype(int dtype) { return dtype >= FMI_F32 && dtype <= FMI_I
 // fmi_fused_half_*.hip translation units.
 inline bool is_half_dtype(int dtype) { return dtype == FMI_F16 || dtype == FMI_BF16; }
 
+// The dtype ARGUMENT of a P-way call may carry FMI_ACC_F32 (include/fmi_dev.h): its storage dtype, which sizes,
+// alignment, order_sensitive, fused_covers and with_dtype take, and whether the program's values are kept in f32.
+inline int storage_dtype(int dtype_arg) { return dtype_arg & ~FMI_ACC_F32; }
+inline bool accumulates_f32(int dtype_arg) { return (dtype_arg & FMI_ACC_F32) != 0; }
+// What every entry point does with its dtype argument, once: the flag is valid on the two 16-bit float dtypes alone
+// (FMI_ERR_INVALID naming the dtype otherwise), and it is dropped where it cannot change a bit: max / min are
+// selections, and a pairwise call (pway = false) or a single peer makes no second rounding. *canon: the storage
+// dtype, with the flag where the call accumulates in f32. An unknown storage dtype is left to the caller's own check.
+inline int canonical_dtype(int op, int dtype_arg, bool pway, int P, int* canon) {
+    *canon = storage_dtype(dtype_arg);
+    if (!accumulates_f32(dtype_arg)) return FMI_OK;
+    if (!is_half_dtype(*canon))
+        return fail(FMI_ERR_INVALID, "dtype " + std::to_string(dtype_arg) + ": FMI_ACC_F32 is valid only as FMI_F16 | FMI_ACC_F32 "
+                                     "or FMI_BF16 | FMI_ACC_F32");
+    if (pway && P != 1 && (op == FMI_OP_SUM || op == FMI_OP_PROD)) *canon |= FMI_ACC_F32;
+    return FMI_OK;
+}
+
 // Which (op, dtype, algorithm, P) have a single-pass kernel (fused, or built from fused blocks): the core dtypes and
 // the 16-bit floats, everywhere. The 8/16-bit integers take run_program_stepwise. No (op, algorithm, P) of the
 // 16-bit floats is held back: none of their kernels needs scratch memory, which is what `op` is
@@ -155,6 +173,20 @@ int launch_fused_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t
 // rank_aware: the rank-selecting allreduce (float max / min at P != 2^k).
 int launch_fused_half(int alg, bool rank_aware, int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int rank,
                       hipStream_t s);
+// FMI_ACC_F32 (dtype = storage dtype | FMI_ACC_F32, op sum or prod, 2 <= P <= 16): launch_fused hands these to
+// launch_fused_acc32 (fmi_fused_acc32.hip), which picks the family's translation unit (fmi_fused_acc32_*.hip); the
+// units take the storage dtype.
+int launch_fused_acc32(int alg, int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_acc32_allreduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_acc32_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_acc32_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_acc32_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_acc32_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_acc32_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+// The fallback's streaming conversions (fmi_acc32_convert.hip), any alignment: dst[i] = (float)src[i] (exact) and
+// dst[i] = the storage type's rounding of src[i]. dtype: FMI_F16 or FMI_BF16.
+int launch_widen_f32(int dtype, float* dst, const void* src, size_t n, hipStream_t s);
+int launch_narrow_f32(int dtype, void* dst, const float* src, size_t n, hipStream_t s);
 int launch_fused_half_allreduce(int op, int dtype, bool rank_aware, int P, const PeerPtrs& ptrs, size_t n, int rank,
                                 hipStream_t s);
 int launch_fused_half_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);

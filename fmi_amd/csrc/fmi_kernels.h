@@ -266,6 +266,86 @@ __device__ __forceinline__ Lanes<T, W> combine(const Lanes<T, W>& a, const Lanes
     }
 }
 
+// f32 accumulation of the 16-bit floats (FMI_ACC_F32, include/fmi_dev.h): the fused kernels' group functions take the
+// storage type T (what is loaded and stored) and the value type V (what the program's values are held and combined
+// in) as two parameters; the kernels take one element parameter E and read the two from Elem<E> (so that the plain
+// instantiations keep their names and their code). V = T everywhere but at E = Acc32<T>, T _Float16 / __bf16: each
+// loaded lane group is widened once (exact), the steps are combine<Op, float, W> (v_pk_add_f32 / v_pk_mul_f32), and
+// each stored value is narrowed once, round-to-nearest-even with subnormals kept and NaN staying NaN: the conversion
+// Op::apply<T> ends with (v_cvt_pk_bf16_f32; v_cvt_f16_f32 / v_cvt_pk_f16_f32, never the rtz pack). At V = T the group
+// functions keep their expressions as they were (if constexpr), so the plain kernels compile to the same code.
+template <class T>
+struct Acc32 {};  // element parameter of a fused kernel: T stored, f32 values (sum / prod, whose bits no rank changes)
+template <class E>
+struct Elem {
+    using storage = E;
+    using value = E;
+};
+template <class T>
+struct Elem<Acc32<T>> {
+    using storage = T;
+    using value = float;
+};
+
+template <class V, class T, int W>
+__device__ __forceinline__ Lanes<V, W> to_value(const Lanes<T, W>& x) {
+    if constexpr (std::is_same_v<V, T>) {
+        return x;
+    } else {
+        static_assert(std::is_same_v<V, float> && is_half_float_v<T>, "f32 values of 16-bit float storage");
+        Lanes<V, W> r;
+        if constexpr (std::is_same_v<T, __bf16> && W % 2 == 0) {
+            struct Words {
+                uint32_t w[W / 2];
+            };
+            const Words p = __builtin_bit_cast(Words, x);
+#pragma unroll
+            for (int k = 0; k < W / 2; ++k) {
+                r.v[2 * k] = __builtin_bit_cast(float, p.w[k] << 16);
+                r.v[2 * k + 1] = __builtin_bit_cast(float, p.w[k] & 0xFFFF0000u);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < W; ++k) r.v[k] = static_cast<float>(x.v[k]);
+        }
+        return r;
+    }
+}
+
+template <class T, class V, int W>
+__device__ __forceinline__ Lanes<T, W> to_storage(const Lanes<V, W>& x) {
+    if constexpr (std::is_same_v<V, T>) {
+        return x;
+    } else {
+        static_assert(std::is_same_v<V, float> && is_half_float_v<T>, "f32 values of 16-bit float storage");
+        Lanes<T, W> r;
+        if constexpr (std::is_same_v<T, __bf16> && W % 2 == 0) {
+            struct Words {
+                uint32_t w[W / 2];
+            } p;
+#pragma unroll
+            for (int k = 0; k < W / 2; ++k) {
+                f32x2 y;
+                y.x = x.v[2 * k];
+                y.y = x.v[2 * k + 1];
+                p.w[k] = __builtin_bit_cast(uint32_t, __builtin_convertvector(y, bf16x2));
+            }
+            r = __builtin_bit_cast(Lanes<T, W>, p);
+        } else {
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                float f = x.v[k];
+                // One element per lane (the ragged tail): keep the narrowing apart from the combine before it. The
+                // compiler otherwise fuses an f32 multiply and the conversion to f16 into v_fma_mixlo_f16 x, y, +0,
+                // and a product that is -0 comes out as +0.
+                if constexpr (W == 1) asm("" : "+v"(f));
+                r.v[k] = static_cast<T>(f);
+            }
+        }
+        return r;
+    }
+}
+
 // Buffer-op form of the fused kernels' 16-B accesses (pol = 1, FMI_TUNE_FUSED_POLICY): every access of a
 // 256-thread tile goes through a descriptor based at the tile's first byte of that bucket (a uniform
 // 64-bit address, so any bucket size) with the lane's 32-bit byte offset, and carries an explicit cache
@@ -458,10 +538,13 @@ __device__ __forceinline__ void run_steps(Lanes<T, W>* v, std::index_sequence<S.
     ((v[P + S] = combine<Op, T, W, REWIDEN>(v[kStepA<ALG, P, S>], v[kStepB<ALG, P, S>])), ...);
 }
 
-template <class T, int W, int P, size_t... I>
-__device__ __forceinline__ void load_peers(Lanes<T, W>* v, const PeerPtrs& ptrs, size_t elem,
+template <class T, int W, int P, class V, size_t... I>
+__device__ __forceinline__ void load_peers(Lanes<V, W>* v, const PeerPtrs& ptrs, size_t elem,
                                            std::index_sequence<I...>) {
-    ((v[I] = load_lanes<kFusedNT, T, W>(static_cast<const T*>(ptrs.in[I]) + elem)), ...);
+    if constexpr (std::is_same_v<V, T>)
+        ((v[I] = load_lanes<kFusedNT, T, W>(static_cast<const T*>(ptrs.in[I]) + elem)), ...);
+    else
+        ((v[I] = to_value<V>(load_lanes<kFusedNT, T, W>(static_cast<const T*>(ptrs.in[I]) + elem))), ...);
 }
 
 // The value as an opaque register operand. A select chain over loads from one array (pick_rank below) is
@@ -496,44 +579,57 @@ __device__ __forceinline__ Lanes<T, W> pick_rank(const Lanes<T, W>* v, int rank,
     return r;
 }
 
-template <class T, int W, int ALG, int P, size_t... R>
-__device__ __forceinline__ void store_all(const Lanes<T, W>* v, const PeerPtrs& ptrs, size_t elem,
+template <class T, int W, int ALG, int P, class V, size_t... R>
+__device__ __forceinline__ void store_all(const Lanes<V, W>* v, const PeerPtrs& ptrs, size_t elem,
                                           std::index_sequence<R...>) {
-    ((store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[R]) + elem, v[kOut<ALG, P, R>])), ...);
+    if constexpr (std::is_same_v<V, T>)
+        ((store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[R]) + elem, v[kOut<ALG, P, R>])), ...);
+    else
+        ((store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[R]) + elem, to_storage<T>(v[kOut<ALG, P, R>]))), ...);
 }
 
-template <class T, int W, int P, size_t... I>
-__device__ __forceinline__ void load_peers_tile(Lanes<T, W>* v, const PeerPtrs& ptrs, size_t tile_byte, unsigned lane_byte,
+template <class T, int W, int P, class V, size_t... I>
+__device__ __forceinline__ void load_peers_tile(Lanes<V, W>* v, const PeerPtrs& ptrs, size_t tile_byte, unsigned lane_byte,
                                                 std::index_sequence<I...>) {
-    ((v[I] = load_tile<kFusedLoadAux, T, W>(ptrs.in[I], tile_byte, lane_byte)), ...);
+    if constexpr (std::is_same_v<V, T>)
+        ((v[I] = load_tile<kFusedLoadAux, T, W>(ptrs.in[I], tile_byte, lane_byte)), ...);
+    else
+        ((v[I] = to_value<V>(load_tile<kFusedLoadAux, T, W>(ptrs.in[I], tile_byte, lane_byte))), ...);
 }
 
 // ALL_RANKS: honour `rank` (output = the value peer `rank` holds). Needed only where operand order can
 // change bits (float max/min on ±0); otherwise rank 0's expression is bit-identical for every peer.
-template <class Op, class T, int ALG, int P, bool ALL_RANKS, int W>
+// V: the value type (to_value / to_storage above); T itself but in the acc32 kernels.
+template <class Op, class T, int ALG, int P, bool ALL_RANKS, int W, class V = T>
 __device__ __forceinline__ void tree_group(const PeerPtrs& ptrs, int rank, size_t elem) {
-    Lanes<T, W> v[P + kNumSteps<ALG, P>];
+    Lanes<V, W> v[P + kNumSteps<ALG, P>];
     load_peers<T, W, P>(v, ptrs, elem, std::make_index_sequence<P>{});
-    run_steps<Op, T, W, ALG, P, kRewidenFused<T, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
-    Lanes<T, W> r;
+    run_steps<Op, V, W, ALG, P, kRewidenFused<V, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
+    Lanes<V, W> r;
     if constexpr (ALL_RANKS)
-        r = pick_rank<T, W, ALG, P>(v, rank, std::make_index_sequence<P>{});
+        r = pick_rank<V, W, ALG, P>(v, rank, std::make_index_sequence<P>{});
     else
         r = v[kOut<ALG, P, 0>];
-    store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[0]) + elem, r);
+    if constexpr (std::is_same_v<V, T>)
+        store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[0]) + elem, r);
+    else
+        store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[0]) + elem, to_storage<T>(r));
 }
 
-template <class Op, class T, int ALG, int P, bool ALL_RANKS, int W>
+template <class Op, class T, int ALG, int P, bool ALL_RANKS, int W, class V = T>
 __device__ __forceinline__ void tree_group_tile(const PeerPtrs& ptrs, int rank, size_t tile_byte, unsigned lane_byte) {
-    Lanes<T, W> v[P + kNumSteps<ALG, P>];
+    Lanes<V, W> v[P + kNumSteps<ALG, P>];
     load_peers_tile<T, W, P>(v, ptrs, tile_byte, lane_byte, std::make_index_sequence<P>{});
-    run_steps<Op, T, W, ALG, P, kRewidenFused<T, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
-    Lanes<T, W> r;
+    run_steps<Op, V, W, ALG, P, kRewidenFused<V, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
+    Lanes<V, W> r;
     if constexpr (ALL_RANKS)
-        r = pick_rank<T, W, ALG, P>(v, rank, std::make_index_sequence<P>{});
+        r = pick_rank<V, W, ALG, P>(v, rank, std::make_index_sequence<P>{});
     else
         r = v[kOut<ALG, P, 0>];
-    store_tile<kTreeStoreAux, T, W>(ptrs.out[0], tile_byte, lane_byte, r);
+    if constexpr (std::is_same_v<V, T>)
+        store_tile<kTreeStoreAux, T, W>(ptrs.out[0], tile_byte, lane_byte, r);
+    else
+        store_tile<kTreeStoreAux, T, W>(ptrs.out[0], tile_byte, lane_byte, to_storage<T>(r));
 }
 
 // Launched with one thread per 16-B lane group up to kFusedGridCap workgroups; beyond that (buckets of
@@ -542,68 +638,82 @@ inline constexpr size_t kFusedGridCap = size_t(1) << 22;
 
 // pol = 1: buffer accesses tile by tile (the tile index is uniform, so each tile's descriptors are scalar);
 // pol = 0: global accesses.
-template <class Op, class T, int ALG, int P, bool ALL_RANKS>
+// E: the element type, or Acc32<T> (T stored, f32 values).
+template <class Op, class E, int ALG, int P, bool ALL_RANKS>
 __global__ void __launch_bounds__(256) tree_kernel(PeerPtrs ptrs, size_t n, int rank, int pol) {
+    using T = typename Elem<E>::storage;
+    using V = typename Elem<E>::value;
     constexpr int W = kVecLanes<T>;
     const size_t nvec = n / W;
     if (pol == 1) {
         const size_t B = blockDim.x;
         for (size_t tile = blockIdx.x; tile * B < nvec; tile += gridDim.x)
             if (tile * B + threadIdx.x < nvec)
-                tree_group_tile<Op, T, ALG, P, ALL_RANKS, W>(ptrs, rank, tile * B * 16, threadIdx.x * 16u);
+                tree_group_tile<Op, T, ALG, P, ALL_RANKS, W, V>(ptrs, rank, tile * B * 16, threadIdx.x * 16u);
     } else {
         const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
         for (size_t g = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; g < nvec; g += stride)
-            tree_group<Op, T, ALG, P, ALL_RANKS, W>(ptrs, rank, g * W);
+            tree_group<Op, T, ALG, P, ALL_RANKS, W, V>(ptrs, rank, g * W);
     }
     const size_t first = nvec * W;
-    if (blockIdx.x == 0 && first + threadIdx.x < n) tree_group<Op, T, ALG, P, ALL_RANKS, 1>(ptrs, rank, first + threadIdx.x);
+    if (blockIdx.x == 0 && first + threadIdx.x < n) tree_group<Op, T, ALG, P, ALL_RANKS, 1, V>(ptrs, rank, first + threadIdx.x);
 }
 
 // Carry programs (sched::is_carry_alg) leave output 0 alone: value 0 is the carry itself.
-template <class T, int W, int ALG, int P, size_t... R>
-__device__ __forceinline__ void store_after_carry(const Lanes<T, W>* v, const PeerPtrs& ptrs, size_t elem,
+template <class T, int W, int ALG, int P, class V, size_t... R>
+__device__ __forceinline__ void store_after_carry(const Lanes<V, W>* v, const PeerPtrs& ptrs, size_t elem,
                                                   std::index_sequence<R...>) {
-    ((store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[R + 1]) + elem, v[kOut<ALG, P, R + 1>])), ...);
+    if constexpr (std::is_same_v<V, T>)
+        ((store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[R + 1]) + elem, v[kOut<ALG, P, R + 1>])), ...);
+    else
+        ((store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[R + 1]) + elem, to_storage<T>(v[kOut<ALG, P, R + 1>]))), ...);
 }
 
-template <class Op, class T, int ALG, int P, int W>
+template <class Op, class T, int ALG, int P, int W, class V = T>
 __device__ __forceinline__ void scan_group(const PeerPtrs& ptrs, size_t elem) {
-    Lanes<T, W> v[P + kNumSteps<ALG, P>];
+    Lanes<V, W> v[P + kNumSteps<ALG, P>];
     load_peers<T, W, P>(v, ptrs, elem, std::make_index_sequence<P>{});
-    run_steps<Op, T, W, ALG, P>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
+    run_steps<Op, V, W, ALG, P>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
     if constexpr (sched::is_carry_alg(ALG))
         store_after_carry<T, W, ALG, P>(v, ptrs, elem, std::make_index_sequence<P - 1>{});
     else
         store_all<T, W, ALG, P>(v, ptrs, elem, std::make_index_sequence<P>{});
 }
 
-template <class Op, class T, int ALG, int P, int W>
+template <class Op, class T, int ALG, int P, int W, class V = T>
 __device__ __forceinline__ void scan_group_tile(const PeerPtrs& ptrs, size_t tile_byte, unsigned lane_byte) {
-    Lanes<T, W> v[P + kNumSteps<ALG, P>];
+    Lanes<V, W> v[P + kNumSteps<ALG, P>];
     load_peers_tile<T, W, P>(v, ptrs, tile_byte, lane_byte, std::make_index_sequence<P>{});
-    run_steps<Op, T, W, ALG, P>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
+    run_steps<Op, V, W, ALG, P>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
     constexpr int first_out = sched::is_carry_alg(ALG) ? 1 : 0;  // carry programs leave output 0 alone
     [&]<size_t... R>(std::index_sequence<R...>) {
-        ((store_tile<kScanStoreAux, T, W>(ptrs.out[R + first_out], tile_byte, lane_byte, v[kOut<ALG, P, R + first_out>])), ...);
+        if constexpr (std::is_same_v<V, T>)
+            ((store_tile<kScanStoreAux, T, W>(ptrs.out[R + first_out], tile_byte, lane_byte, v[kOut<ALG, P, R + first_out>])), ...);
+        else
+            ((store_tile<kScanStoreAux, T, W>(ptrs.out[R + first_out], tile_byte, lane_byte,
+                                              to_storage<T>(v[kOut<ALG, P, R + first_out>]))),
+             ...);
     }(std::make_index_sequence<P - first_out>{});
 }
 
-template <class Op, class T, int ALG, int P>
+// E: as for tree_kernel; with Acc32<T> every stored prefix (or partial) is its own f32 value, narrowed once.
+template <class Op, class E, int ALG, int P>
 __global__ void __launch_bounds__(256) scan_kernel(PeerPtrs ptrs, size_t n, int pol) {
+    using T = typename Elem<E>::storage;
+    using V = typename Elem<E>::value;
     constexpr int W = kVecLanes<T>;
     const size_t nvec = n / W;
     if (pol == 1) {
         const size_t B = blockDim.x;
         for (size_t tile = blockIdx.x; tile * B < nvec; tile += gridDim.x)
-            if (tile * B + threadIdx.x < nvec) scan_group_tile<Op, T, ALG, P, W>(ptrs, tile * B * 16, threadIdx.x * 16u);
+            if (tile * B + threadIdx.x < nvec) scan_group_tile<Op, T, ALG, P, W, V>(ptrs, tile * B * 16, threadIdx.x * 16u);
     } else {
         const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
         for (size_t g = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; g < nvec; g += stride)
-            scan_group<Op, T, ALG, P, W>(ptrs, g * W);
+            scan_group<Op, T, ALG, P, W, V>(ptrs, g * W);
     }
     const size_t first = nvec * W;
-    if (blockIdx.x == 0 && first + threadIdx.x < n) scan_group<Op, T, ALG, P, 1>(ptrs, first + threadIdx.x);
+    if (blockIdx.x == 0 && first + threadIdx.x < n) scan_group<Op, T, ALG, P, 1, V>(ptrs, first + threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -43,6 +43,20 @@ class DType(enum.IntEnum):
     BF16 = 11
 
 
+# fmi_dev.h's FMI_ACC_F32: ORed into the dtype argument of a P-way call on F16 / BF16 buckets, the program's values
+# are kept in f32 and every stored output is rounded to the storage type once (`accumulate_f32=True` below).
+ACC_F32 = 0x100
+
+
+def acc_dtype(dtype: "DType", accumulate_f32: bool) -> int:
+    """The dtype argument of a P-way call: the storage dtype, with ACC_F32 when `accumulate_f32`."""
+    if not accumulate_f32:
+        return int(dtype)
+    if dtype not in (DType.F16, DType.BF16):
+        raise ValueError(f"accumulate_f32 needs F16 or BF16 buckets, got {DType(dtype).name}")
+    return int(dtype) | ACC_F32
+
+
 class Alg(enum.IntEnum):
     """Evaluation orders of the reference collectives (src/comm/PeerToPeer.cpp)."""
     ALLREDUCE = 0   # allreduce_no_order  :96-130
@@ -354,20 +368,26 @@ def _ptr_array(buckets: Sequence[Bucket]):
     return arr
 
 
-def reduce_tree(op: Op, alg: Alg, out: Bucket, ins: Sequence[Bucket], rank: int = 0, stream=None) -> None:
-    """P-way reduction with a reference collective's bracketing (see include/fmi_dev.h)."""
+def reduce_tree(op: Op, alg: Alg, out: Bucket, ins: Sequence[Bucket], rank: int = 0, stream=None,
+                accumulate_f32: bool = False) -> None:
+    """P-way reduction with a reference collective's bracketing (see include/fmi_dev.h). accumulate_f32 (F16 / BF16
+    buckets): the same program on f32 values, the result rounded to the storage type once."""
+    dtype = acc_dtype(out.dtype, accumulate_f32)
     _check_peers(out, ins)
-    _lib.call("fmi_dev_reduce_tree", int(op), int(out.dtype), int(alg), out.ptr, _ptr_array(ins), len(ins), rank,
+    _lib.call("fmi_dev_reduce_tree", int(op), dtype, int(alg), out.ptr, _ptr_array(ins), len(ins), rank,
               out.n, _sptr(stream))
 
 
-def scan_peers(op: Op, alg: Alg, outs: Sequence[Bucket], ins: Sequence[Bucket], stream=None) -> None:
-    """Peer-axis inclusive scan with the bracketing of reference scan_no_order / scan_ltr."""
+def scan_peers(op: Op, alg: Alg, outs: Sequence[Bucket], ins: Sequence[Bucket], stream=None,
+               accumulate_f32: bool = False) -> None:
+    """Peer-axis inclusive scan with the bracketing of reference scan_no_order / scan_ltr. accumulate_f32 (F16 /
+    BF16 buckets): the same program on f32 values, every prefix rounded to the storage type once."""
     if len(outs) != len(ins):
         raise ValueError("scan_peers: one output bucket per peer")
+    dtype = acc_dtype(outs[0].dtype, accumulate_f32)
     _check_peers(outs[0], ins)  # O(P): every bucket, in or out, against the first output
     _check_peers(outs[0], outs)
-    _lib.call("fmi_dev_scan_peers", int(op), int(outs[0].dtype), int(alg), _ptr_array(outs), _ptr_array(ins),
+    _lib.call("fmi_dev_scan_peers", int(op), dtype, int(alg), _ptr_array(outs), _ptr_array(ins),
               len(ins), outs[0].n, _sptr(stream))
 
 

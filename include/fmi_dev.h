@@ -82,6 +82,33 @@ typedef enum {
     FMI_F16 = 10, FMI_BF16 = 11
 } fmi_dtype_t;
 
+/* f32 accumulation: a modifier bit on the dtype ARGUMENT of a call, valid only as FMI_F16 | FMI_ACC_F32 or
+ * FMI_BF16 | FMI_ACC_F32 (with any other dtype: FMI_ERR_INVALID naming the dtype). The buckets stay 16-bit; a P-way
+ * program at T | FMI_ACC_F32
+ *   1. widens every input element to f32 (exact),
+ *   2. runs the SAME program in the SAME order (the bracketing of `alg`) with f32 combines: IEEE round-to-nearest-
+ *      even, subnormals kept, no contraction, exactly what the FMI_F32 kernels compute,
+ *   3. narrows every value the call STORES to T once (round-to-nearest-even, subnormals kept, NaN stays NaN): the
+ *      result of fmi_dev_reduce_tree, every prefix of fmi_dev_scan_peers, every partial fmi_comm_reduce_sendbuf leaves
+ *      in a sendbuf, each its own f32 value rounded once.
+ * In one line: out = narrow(F32_program(widen(x))). What a gradient bucket that travels in bf16 wants: the plain
+ * dtypes round the running value to 8 (bf16) or 11 (f16) significant bits after every combine.
+ * MAX / MIN are selections, which f32 accumulation cannot change: the flag is accepted and dropped, and the plain
+ * kernels run (per-rank bits as before). A single combine is already "widen, op, round once": the pairwise calls
+ * (fmi_dev_reduce_pair, _batch, fmi_dev_combine, fmi_host_reduce_pair) accept the flag and drop it, and P = 1 stays
+ * the copy. A NaN made by SUM / PROD is some NaN. Entry points that only store (fmi_dev_fill_synthetic*) take the
+ * plain dtype and answer the flag with FMI_ERR_INVALID.
+ * SUM / PROD at 2 <= P <= 16 on 16-B aligned buckets run one fused kernel (P reads, the stores, nothing else), at
+ * all five algorithms and for reduce partials. Any other call (P > 16, unaligned buckets) widens every input into an
+ * f32 temporary, runs the library's own FMI_F32 program on those and narrows every stored output: the same
+ * definition by construction, at P * n * 4 bytes of temporaries (+ n * 4 for fmi_dev_reduce_tree's result) in an
+ * allocation of the library's own (FMI_ERR_ALLOC if it cannot be had).
+ * The communicator calls (fmi_comm_allreduce on paths TREE and DIRECT, _allreduce_host, _reduce, _reduce_sendbuf,
+ * _scan) accept it: the wire stays 16-bit and only the shard step changes; every rank passes the same dtype argument,
+ * as every other argument. FMI_PATH_RCCL with the flag (SUM / PROD) is FMI_ERR_UNSUPPORTED: RCCL's reduction has its
+ * own order and rounding. Additive: fmi_abi_version() stays 1, no new symbol. */
+#define FMI_ACC_F32 0x100   /* valid only as FMI_F16 | FMI_ACC_F32 or FMI_BF16 | FMI_ACC_F32 */
+
 /* Evaluation orders reproduced by the P-way kernels; each is the combine order of one reference
  * collective, so a P-bucket reduction on one device is bit-identical to the distributed one. */
 typedef enum {
@@ -173,7 +200,8 @@ int fmi_event_elapsed_ms(float* ms, fmi_event_t start, fmi_event_t stop);
  * fmi_stream_create, calls on that stream are recorded, not run. Capture-safe: fmi_dev_reduce_pair,
  * fmi_dev_combine, the d2d / memset copies, and fmi_dev_reduce_tree / fmi_dev_scan_peers up to 16 peers
  * (one fused kernel each) on 16-B aligned f32 / f64 / i32 / i64 / f16 / bf16 buckets, at every algorithm: for
- * FMI_F16 / FMI_BF16 that includes FMI_ALG_REDUCE_LTR and FMI_ALG_SCAN_LTR. Beyond 16 peers a call on such buckets
+ * FMI_F16 / FMI_BF16 that includes FMI_ALG_REDUCE_LTR and FMI_ALG_SCAN_LTR. FMI_ACC_F32 calls at P <= 16 on aligned buckets are capture-safe (one fused
+ * kernel each); beyond 16 peers or on unaligned buckets they need the f32 temporaries and are not. Beyond 16 peers a call on such buckets
  * is capture-safe exactly where it needs no temporary bucket, which at FMI_TUNE_BLOCKS_ONE_PASS = 1 (the default)
  * is, the same for the six dtypes: FMI_ALG_ALLREDUCE at P <= 31 and P = 32, 48, 64, 80, 96, 112; FMI_ALG_REDUCE at
  * P <= 128; FMI_ALG_SCAN at P <= 143; FMI_ALG_SCAN_LTR at any P; FMI_ALG_REDUCE_LTR at P <= 128, and beyond when

@@ -16,6 +16,16 @@ With --forms, the fused forms beyond the 8-way allreduce instead, each family al
   scan32        SCAN over 32 peers: f32 sum, bf16 sum                   (64 x 256 MiB; 2 groups)
   allreduce13   (only with --only) ALLREDUCE over 13 peers, rank 5: f32 max, bf16 max (14 x 256 MiB; 3 groups)
 
+With --acc32, the f32-accumulating kernels (FMI_ACC_F32, accumulate_f32=True) beside the plain 16-bit kernel of the same
+shape (same bytes) and the f32 kernel of equal bytes, sum, for bf16 and f16:
+
+  allreduce8    ALLREDUCE over 8 peers   (9 x 256 MiB per launch; 3 groups)
+  scan8         SCAN over 8 peers        (16 x 256 MiB; 3 groups)
+  reduce_ltr16  REDUCE_LTR over 16 peers (17 x 256 MiB; 2 groups)
+  scan16        SCAN over 16 peers       (32 x 256 MiB; 2 groups)
+
+Each line carries its own spread over the three passes, its ratio to the plain 16-bit kernel and to f32 per pass.
+
 The yardstick of a 16-bit kernel is the f32 kernel of the same family and op. The same rows run against any
 library (FMI_DEV_LIB), e.g. one built from an earlier commit whose 16-bit programs ran as pairwise passes.
 
@@ -26,6 +36,7 @@ the spread of that f32 kernel against itself over the three passes ((max - min) 
 than that spread below f32 is a finding.
 
     python3 tools/half_kernels.py [--out profiles/NAME.jsonl]
+    python3 tools/half_kernels.py --acc32 [--only allreduce8,scan16] [--out profiles/NAME.jsonl]
     python3 tools/half_kernels.py --forms [--only reduce_ltr8,reduce32] [--label NAME] [--out profiles/NAME.jsonl]
 """
 import argparse
@@ -133,6 +144,65 @@ def forms(args):
         fmi_amd.sync()
 
 
+def _reduce_acc(alg, P):
+    return lambda g, acc: fmi_amd.reduce_tree(Op.SUM, alg, g[P], g[:P], accumulate_f32=acc)
+
+
+def _scan_acc(alg, P):
+    return lambda g, acc: fmi_amd.scan_peers(Op.SUM, alg, g[P:], g[:P], accumulate_f32=acc)
+
+
+# family: (peers, buckets per group, rotating groups, launch(group, accumulate_f32))
+ACC32 = {
+    "allreduce8": (8, 9, 3, _reduce_acc(Alg.ALLREDUCE, 8)),
+    "scan8": (8, 16, 3, _scan_acc(Alg.SCAN, 8)),
+    "reduce_ltr16": (16, 17, 2, _reduce_acc(Alg.REDUCE_LTR, 16)),
+    "scan16": (16, 32, 2, _scan_acc(Alg.SCAN, 16)),
+}
+ACC32_ROWS = [("f32", False), ("bf16", False), ("bf16", True), ("f16", False), ("f16", True)]
+
+
+def acc32(args):
+    nbytes = args.mib * MIB
+    for fam in (args.only.split(",") if args.only else list(ACC32)):
+        P, count, sets, launch = ACC32[fam]
+        groups = {}
+        for name, (dt, esz) in DTYPES.items():
+            groups[name] = [Bucket.group(count, nbytes // esz, dt) for _ in range(sets)]
+            for g in groups[name]:
+                for p in range(P):
+                    g[p].fill_synthetic(11, p)
+        fmi_amd.sync()
+        rates = {r: [] for r in ACC32_ROWS}
+        for _ in range(PASSES):
+            for name, acc in ACC32_ROWS:
+                gs = groups[name]
+                ms = timed(lambda k: launch(gs[k % len(gs)], acc), args.iters, sets)
+                rates[(name, acc)].append(count * nbytes / (ms * 1e-3))
+        lines = []
+        for name, acc in ACC32_ROWS:
+            mine, f32, plain = rates[(name, acc)], rates[("f32", False)], rates[(name, False)]
+            spread = lambda xs: round((max(xs) - min(xs)) / statistics.median(xs), 4)  # noqa: E731
+            lines.append({"tool": "tools/half_kernels.py --acc32", "label": args.label,
+                          "kernel": f"{fam} {name}{' acc32' if acc else ''} sum", "peers": P, "bucket_mib": args.mib,
+                          "algorithmic_bytes": count * nbytes, "iters_per_pass": args.iters, "passes": PASSES,
+                          "rotating_sets": sets, "GB_s_per_pass": [round(r / 1e9, 1) for r in mine],
+                          "GB_s": round(statistics.median(mine) / 1e9, 1), "spread": spread(mine),
+                          "ratio_to_plain_per_pass": [round(r / y, 4) for r, y in zip(mine, plain)],
+                          "ratio_to_plain": round(statistics.median([r / y for r, y in zip(mine, plain)]), 4),
+                          "plain_spread": spread(plain),
+                          "ratio_to_f32_per_pass": [round(r / y, 4) for r, y in zip(mine, f32)],
+                          "ratio_to_f32": round(statistics.median([r / y for r, y in zip(mine, f32)]), 4),
+                          "f32_spread": spread(f32),
+                          "timing": "two HIP events around back-to-back launches on the library stream"})
+        emit(lines, args.out)
+        for gs in groups.values():
+            for g in gs:
+                for b in g:
+                    b.free()
+        fmi_amd.sync()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256, help="bytes per bucket")
@@ -141,10 +211,13 @@ def main():
     ap.add_argument("--tree-sets", type=int, default=3)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--forms", action="store_true", help="the fused forms (see above) instead of pair / tree8")
-    ap.add_argument("--only", default=None, help="with --forms: a comma-separated subset of the families")
+    ap.add_argument("--acc32", action="store_true", help="FMI_ACC_F32 beside the plain 16-bit and the f32 kernels")
+    ap.add_argument("--only", default=None, help="with --forms / --acc32: a comma-separated subset of the families")
     ap.add_argument("--label", default="tree", help="with --forms: what the lines are tagged with (e.g. the commit)")
     args = ap.parse_args()
     fmi_amd.init(0)
+    if args.acc32:
+        return acc32(args)
     if args.forms:
         return forms(args)
     nbytes = args.mib * MIB

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Register and scratch use of the 16-bit float kernels (fmi_amd/csrc/fmi_fused_half_*.hip), read from the
+"""Register and scratch use of the 16-bit float kernels (fmi_amd/csrc/fmi_fused_half_*.hip, and the f32-accumulating
+ones of FMI_ACC_F32: fmi_fused_acc32_*.hip with the fallback's conversions in fmi_acc32_convert.hip), read from the
 compiler's own remarks: each unit is compiled device-only for gfx950 with -Rpass-analysis=kernel-resource-usage,
 and every kernel's VGPRs / AGPRs / scratch / occupancy are collected. Exits 1 if any kernel uses scratch.
 
     python3 tools/half_resource_usage.py                 # compile (a few minutes), print the summary per family
     python3 tools/half_resource_usage.py --logs DIR      # parse remark logs kept from a build instead
     python3 tools/half_resource_usage.py --core          # the f32 kernels of the core units, for the comparison
+    python3 tools/half_resource_usage.py --acc32         # the FMI_ACC_F32 units alone
 
 The summary groups kernels by family, dtype and op and gives the range over P.
 """
@@ -57,24 +59,31 @@ DTYPES = {"DF16_": "f16", "DF16b": "bf16", "f": "f32", "d": "f64", "i": "i32", "
 def describe(mangled):
     """(kernel, dtype, op, the remaining template arguments) from a kernel's Itanium-mangled name, e.g.
     _ZN3fmi3dev11tree_kernelINS0_5OpSumEDF16_Li7ELi32ELb0EEEv...: tree_kernel<OpSum, _Float16, 7, 32, false>."""
-    m = re.search(r"(?<=\d)([a-z_]+_kernel)INS\d*_\d(Op[A-Z][a-z]+)E(DF16_|DF16b|[fdil])((?:L[ib]\d+E)*)E", mangled)
+    m = re.search(r"(?<=\d)([a-z_]+_kernel)INS\d*_\d(Op[A-Z][a-z]+)E(NS\d*_5Acc32I)?(DF16_|DF16b|[fdil])(?(3)EE)((?:L[ib]\d+E)*)E",
+                  mangled)
     if not m:
         return None
-    args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(4))]
-    return m.group(1), DTYPES[m.group(3)], m.group(2), ", ".join(args)
+    if m.group(3):  # Acc32<T>: 16-bit storage, f32 values (FMI_ACC_F32)
+        args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(5))]
+        return m.group(1) + "_acc32", DTYPES[m.group(4)], m.group(2), ", ".join(args)
+    args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(5))]
+    return m.group(1), DTYPES[m.group(4)], m.group(2), ", ".join(args)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--logs", help="directory of remark logs (one per unit) to parse instead of compiling")
     ap.add_argument("--core", action="store_true", help="the core units' f32 kernels instead of the half units")
+    ap.add_argument("--acc32", action="store_true", help="the FMI_ACC_F32 units alone")
     ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 8))
     ap.add_argument("--all", action="store_true", help="print every kernel, not the summary")
     a = ap.parse_args()
     if a.logs:
         texts = [open(f).read() for f in sorted(glob.glob(os.path.join(a.logs, "*.log")))]
     else:
-        srcs = CORE if a.core else sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "fmi_fused_half_*.hip")))
+        units = lambda pat: sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, pat)))  # noqa: E731
+        acc32 = units("fmi_fused_acc32_*.hip") + ["fmi_acc32_convert.hip"]
+        srcs = CORE if a.core else acc32 if a.acc32 else units("fmi_fused_half_*.hip") + acc32
         with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
             texts = list(ex.map(remarks, srcs))
     kernels = [k for t in texts for k in parse(t)]
@@ -86,10 +95,13 @@ def main():
         kern, dtype, op, detail = d
         if a.all:
             print(f"{kern}<{op}, {dtype}, {detail}>: vgpr {k['vgpr']} agpr {k['agpr']} scratch {k['scratch']} occupancy {k['occ']}")
-        alg = detail.split(",")[0] if kern in ("tree_kernel", "scan_kernel") else ""
+        fused = kern in ("tree_kernel", "scan_kernel", "tree_kernel_acc32", "scan_kernel_acc32")
+        alg = detail.split(",")[0] if fused else ""
         ranked = kern in ("tree_kernel", "tree_blocks_kernel", "prefold_blocks_kernel") and detail.endswith("true")
+        if kern == "tree_kernel_acc32":
+            detail = detail.rsplit(",", 1)[0]  # no rank-selecting form
         wide = ""
-        if kern in ("tree_kernel", "scan_kernel"):
+        if fused:
             wide = "P>16" if int(detail.split(",")[1]) > 16 else "P<=16"
         groups[(kern, alg, wide, "ranked" if ranked else "", dtype, op)].append(k)
     rng = lambda xs: f"{min(xs)}" if min(xs) == max(xs) else f"{min(xs)}-{max(xs)}"
