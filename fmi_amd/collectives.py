@@ -36,7 +36,7 @@ _TORCH_DTYPE = {torch.float32: DType.F32, torch.float64: DType.F64, torch.int32:
                 torch.int8: DType.I8, torch.uint8: DType.U8, torch.int16: DType.I16, torch.float16: DType.F16,
                 torch.bfloat16: DType.BF16}
 _REDUCE_OP = {Op.SUM: dist.ReduceOp.SUM, Op.PROD: dist.ReduceOp.PRODUCT, Op.MAX: dist.ReduceOp.MAX,
-              Op.MIN: dist.ReduceOp.MIN}
+              Op.MIN: dist.ReduceOp.MIN, Op.AVG: dist.ReduceOp.AVG}
 SHARD_ALIGN = 64  # elements: keeps every shard 256-B aligned for the 16-B vector kernels
 
 
@@ -130,6 +130,9 @@ class ShardedAllreduce:
         if out.numel() != n:
             raise RuntimeError("Dimensions of send and receive data must match")
         L = len(buckets)
+        if op == Op.AVG and L != 1:
+            # the shard step's mean divides by the world size; local rounds would need the peer count instead
+            raise ValueError(f"Op.AVG takes one peer bucket per GPU, got {L}")
         if L & (L - 1):
             # recursive doubling pairs the local peers among themselves only for a power-of-two count
             raise ValueError(f"{L} local peer buckets: a GPU must host a power-of-two number of peers")

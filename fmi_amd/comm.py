@@ -117,7 +117,10 @@ class Comm:
                   stream=None, accumulate_f32: bool = False) -> None:
         """accumulate_f32 (F16 / BF16 buckets, here and in allreduce_host / reduce / scan): every rank's shard is
         reduced on f32 values and rounded to the storage type once (FMI_ACC_F32); the wire stays 16-bit. Every rank
-        passes the same value. Path.RCCL has its own order and rounding and refuses it."""
+        passes the same value. Path.RCCL has its own order and rounding and refuses it.
+        Op.AVG (float buckets; here, in allreduce_host and in reduce): the mean over the ranks, the sum's value times
+        the rounded reciprocal of the rank count before the shard's one store (FMI_OP_AVG); Path.RCCL reduce-scatters
+        with SUM and scales its shard. scan and reduce(sendbuf_partials=True) refuse it."""
         alg = Alg.REDUCE_LTR if ordered else Alg.ALLREDUCE
         arg = acc_dtype(send.dtype, accumulate_f32)
         _lib.call("fmi_comm_allreduce", self.handle, int(op), arg, int(alg), int(path), _p(send), _p(recv), send.n,

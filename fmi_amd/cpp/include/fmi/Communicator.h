@@ -107,6 +107,15 @@ public:
     void reduce(Comm::Data<T>& sendbuf, Comm::Data<T>& recvbuf, Utils::peer_num root, Utils::Function<T> f) {
         if (peer_id == root && sendbuf.size_in_bytes() != recvbuf.size_in_bytes())
             throw std::runtime_error("Dimensions of send and receive data must match");
+        if (f.builtin() == Utils::Op::avg) {
+            if constexpr (Utils::detail::HasMean<T>::value) {
+                mean(sendbuf, recvbuf, f, Utils::reduce, peer_id == root,
+                     [&](Comm::Channel& ch, raw_function raw) { ch.reduce(view(sendbuf), view(recvbuf), root, std::move(raw)); });
+                return;
+            } else {
+                throw std::runtime_error("reduce: Op::avg needs floating-point elements");
+            }
+        }
         const bool ltr = !(f.commutative && f.associative);
         raw_function raw = convert_to_raw_function(f, sendbuf.size_in_bytes());
         auto ch = channel_for({Utils::reduce, sendbuf.size_in_bytes(), ltr, false, !raw.device.valid()}, on_device(sendbuf));
@@ -117,6 +126,15 @@ public:
     void allreduce(Comm::Data<T>& sendbuf, Comm::Data<T>& recvbuf, Utils::Function<T> f) {
         if (sendbuf.size_in_bytes() != recvbuf.size_in_bytes())
             throw std::runtime_error("Dimensions of send and receive data must match");
+        if (f.builtin() == Utils::Op::avg) {
+            if constexpr (Utils::detail::HasMean<T>::value) {
+                mean(sendbuf, recvbuf, f, Utils::allreduce, true,
+                     [&](Comm::Channel& ch, raw_function raw) { ch.allreduce(view(sendbuf), view(recvbuf), std::move(raw)); });
+                return;
+            } else {
+                throw std::runtime_error("allreduce: Op::avg needs floating-point elements");
+            }
+        }
         const bool ltr = !(f.commutative && f.associative);
         raw_function raw = convert_to_raw_function(f, sendbuf.size_in_bytes());
         auto ch = channel_for({Utils::allreduce, sendbuf.size_in_bytes(), ltr, false, !raw.device.valid()},
@@ -129,6 +147,7 @@ public:
     void scan(Comm::Data<T>& sendbuf, Comm::Data<T>& recvbuf, Utils::Function<T> f) {
         if (sendbuf.size_in_bytes() != recvbuf.size_in_bytes())
             throw std::runtime_error("Dimensions of send and receive data must match");
+        if (f.builtin() == Utils::Op::avg) throw std::runtime_error("scan: Op::avg is not valid here (a prefix has no mean)");
         // the reference does not pass left_to_right here (include/Communicator.h:140)
         raw_function raw = convert_to_raw_function(f, sendbuf.size_in_bytes());
         auto ch = channel_for({Utils::scan, sendbuf.size_in_bytes(), false, false, !raw.device.valid()}, on_device(sendbuf));
@@ -193,6 +212,49 @@ private:
         auto it = channels.find(name);
         if (it == channels.end()) throw std::runtime_error("channel '" + name + "' is not registered");
         return it->second;
+    }
+
+    //! Op::avg (fmi_dev.h, FMI_OP_AVG): the collective with Op::sum, its result times the rounded reciprocal of the
+    //! peer count. A channel that hands whole collectives to fmi_comm_* (reduces_mean) takes the op itself; on the
+    //! others the sum runs as ever and the result is finished here, where `holds_result`.
+    template <typename T, typename Run>
+    void mean(Comm::Data<T>& sendbuf, Comm::Data<T>& recvbuf, const Utils::Function<T>& f, Utils::Operation what,
+              bool holds_result, Run run) {
+        Utils::Function<T> sum(Utils::Op::sum, f.accumulate());
+        raw_function raw = convert_to_raw_function(sum, sendbuf.size_in_bytes());
+        auto ch = channel_for({what, sendbuf.size_in_bytes(), false, false, !raw.device.valid()}, on_device(sendbuf));
+        if (ch->reduces_mean() && raw.device.valid()) {
+            raw.device.op = FMI_OP_AVG;
+            run(*ch, std::move(raw));
+            return;
+        }
+        run(*ch, std::move(raw));
+        if (holds_result && num_peers > 1) finish_mean(recvbuf);
+    }
+
+    template <typename A>
+    A mean_of(A sum) const {
+        if constexpr (std::is_same_v<A, Dev::half> || std::is_same_v<A, Dev::bfloat16>)
+            return A(static_cast<float>(sum) * (1.0f / static_cast<float>(num_peers)));
+        else
+            return sum * (static_cast<A>(1) / static_cast<A>(num_peers));
+    }
+    template <typename T>
+    void finish_mean(Comm::Data<T>& d) {
+        T* x = reinterpret_cast<T*>(d.data());
+        *x = mean_of(*x);
+    }
+    template <typename A>
+    void finish_mean(Comm::Data<std::vector<A>>& d) {
+        A* x = reinterpret_cast<A*>(d.data());
+        for (std::size_t i = 0, m = d.size_in_bytes() / sizeof(A); i < m; ++i) x[i] = mean_of(x[i]);
+    }
+    template <typename A>
+    void finish_mean(Comm::Data<Dev::Bucket<A>>& d) {
+        Dev::check(fmi_dev_mean_scale(Dev::dtype_of<A>(), d.data(), d.size_in_bytes() / sizeof(A), static_cast<int>(num_peers),
+                                      nullptr),
+                   "fmi_dev_mean_scale");
+        Dev::check(fmi_stream_sync(nullptr), "fmi_stream_sync");
     }
 
     //! Scalars: *a = f(*a, *b) (reference include/Communicator.h:170-177).

@@ -116,6 +116,9 @@ public:
     //! Whether reductions may be opaque user functions (raw_function::f); device collectives need a
     //! built-in op (raw_function::device).
     virtual bool supports_user_functions() const { return true; }
+    //! Whether reduce / allreduce take FMI_OP_AVG in raw_function::device (channels that hand the whole collective to
+    //! fmi_comm_*). On the others the Communicator runs the sum and scales the result itself.
+    virtual bool reduces_mean() const { return false; }
 
     virtual double get_latency(Utils::peer_num producer, Utils::peer_num consumer, std::size_t size_in_bytes) = 0;
     virtual double get_price(Utils::peer_num producer, Utils::peer_num consumer, std::size_t size_in_bytes) = 0;

@@ -59,6 +59,7 @@ public:
 
     bool supports_host_buffers() const override { return host_ingress_; }
     bool supports_user_functions() const override { return false; }
+    bool reduces_mean() const override { return true; }
 
     //! Accept host buckets too (staged through HBM; allreduce pipelined). pcie_gb_s prices the crossing.
     void set_host_ingress(bool on, double pcie_gb_s = 50.) {
@@ -105,7 +106,7 @@ public:
         const bool is_root = peer_id == root;
         Staged s(this, sendbuf, true);
         Staged r(this, is_root ? recvbuf : channel_data{nullptr, 0, true}, false);
-        if (ordered(f)) {
+        if (ordered(f) || d.op == FMI_OP_AVG) {  // a mean leaves the sendbufs alone: interior partials are sums
             run(fmi_comm_reduce(comm_, d.op, d.dtype, alg, s.ptr(), is_root ? r.ptr() : nullptr, d.count,
                                 static_cast<int>(root), nullptr),
                 "fmi_comm_reduce");

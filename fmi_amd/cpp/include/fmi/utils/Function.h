@@ -23,12 +23,26 @@
 namespace FMI::Dev {
 template <class A>
 class Bucket;
-}
+struct half;
+struct bfloat16;
+}  // namespace FMI::Dev
 
 namespace FMI::Utils {
 
 // Built-in reduction ops; numeric values are the C-ABI's fmi_op_t.
-enum class Op : int { none = -1, sum = FMI_OP_SUM, prod = FMI_OP_PROD, max = FMI_OP_MAX, min = FMI_OP_MIN };
+// Op::avg (FMI_OP_AVG, fmi_dev.h): the mean over the peers of a reduce / allreduce: the sum's value times the
+// correctly rounded reciprocal of the peer count, one multiply (in f32 for Dev::half / Dev::bfloat16, rounded to
+// storage once). Floating-point T, std::vector<A> and Dev::Bucket<A> of floating A, Dev::half or Dev::bfloat16;
+// a Function of any other T throws std::runtime_error. It has no pairwise meaning: operator() throws, scan throws,
+// and the Communicator runs the sum and finishes the result (Comm::Rccl hands the op to fmi_comm_*).
+enum class Op : int {
+    none = -1,
+    sum = FMI_OP_SUM,
+    prod = FMI_OP_PROD,
+    max = FMI_OP_MAX,
+    min = FMI_OP_MIN,
+    avg = FMI_OP_AVG
+};
 
 // What a P-way collective on Dev::half / Dev::bfloat16 elements keeps its running values in: `storage` rounds to the
 // 16-bit type after every combine (the reference's std::plus<__bf16>), `f32` keeps the program's values in f32 and
@@ -63,6 +77,17 @@ A apply_op(Op op, A a, A b) {
         default: throw std::runtime_error("Function: no built-in op");
     }
 }
+
+// Element types that have a mean, and the payload types T built on them.
+template <class A>
+inline constexpr bool mean_elem_v =
+    std::is_floating_point_v<A> || std::is_same_v<A, Dev::half> || std::is_same_v<A, Dev::bfloat16>;
+template <class T>
+struct HasMean : std::bool_constant<std::is_floating_point_v<T>> {};
+template <class A>
+struct HasMean<std::vector<A>> : std::bool_constant<mean_elem_v<A>> {};
+template <class A>
+struct HasMean<Dev::Bucket<A>> : std::bool_constant<mean_elem_v<A>> {};
 
 // The host closure equivalent to a built-in op, for each kind of T.
 template <class T>
@@ -99,14 +124,18 @@ public:
 
     // Built-in op: commutative and associative (the reference's built-ins are registered as such,
     // python/PythonCommunicator.h:133-149), evaluable on the device.
-    explicit Function(Op op) : commutative(true), associative(true), f_(detail::HostBuiltin<T>::make(op)), op_(op) {
+    explicit Function(Op op)
+        : commutative(true), associative(true), f_(op == Op::avg ? nullptr : detail::HostBuiltin<T>::make(op)), op_(op) {
         if (op == Op::none) throw std::runtime_error("Function: Op::none is not a built-in op");
+        if (op == Op::avg && !detail::HasMean<T>::value)
+            throw std::runtime_error("Function: Op::avg needs floating-point elements (float, double, Dev::half, Dev::bfloat16)");
     }
 
     // Built-in op with the accumulation type of P-way collectives (above).
     Function(Op op, Accumulate acc) : Function(op) { acc_ = acc; }
 
     T operator()(T a, T b) const {
+        if (op_ == Op::avg) throw std::runtime_error("Function: Op::avg has no pairwise meaning (a mean of means is no mean)");
         if (!f_) throw std::runtime_error("Function: device-bucket functions have no host evaluation");
         return f_(std::move(a), std::move(b));
     }

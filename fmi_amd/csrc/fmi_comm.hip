@@ -1449,12 +1449,17 @@ int aborted_error() {
 // *kd: the dtype argument in canonical form, what the shard step hands to fmi_dev_reduce_tree / fmi_dev_scan_peers /
 // reduce_partials (FMI_ACC_F32 validated, dropped for max / min); *dtype: its storage dtype, for everything else
 // (sizes, the wire, order_sensitive).
-int check_common(fmi_comm_t comm, int op, int* dtype, int* kd) {
+// FMI_OP_AVG (the mean over the ranks, float dtypes) passes where the call produces a reduction result (`no_avg` NULL);
+// `who` with `no_avg` set refuses it with that reason.
+int check_common(fmi_comm_t comm, int op, int* dtype, int* kd, const char* who = nullptr, const char* no_avg = nullptr) {
     if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
-    if (op < FMI_OP_SUM || op > FMI_OP_MIN) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
+    if (no_avg) FMI_COMM_RC(refuse_avg(op, who, no_avg));
+    if (op != FMI_OP_AVG && (op < FMI_OP_SUM || op > FMI_OP_MIN)) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
     FMI_COMM_RC(canonical_dtype(op, *dtype, true, 0, kd));
     *dtype = storage_dtype(*kd);
     if (dtype_size(*dtype) == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(*dtype));
+    if (op == FMI_OP_AVG && !is_float(*dtype))
+        return refuse_avg(op, "fmi_comm", ("dtype " + std::to_string(*dtype) + " is an integer dtype").c_str());
     if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
     if (static_cast<Comm*>(comm)->t->aborted()) return aborted_error();
     return FMI_OK;
@@ -1714,7 +1719,9 @@ int allreduce_device(Comm* c, int op, int dtype, int kd, int alg, int path, cons
         FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, shard, s));
         FMI_COMM_RC(c->timing.end(s));
     } else {
-        FMI_COMM_RC(c->t->reduce_scatter(op, dtype, src, red, shard, s));
+        // a mean: RCCL's own reduce-scatter with SUM, the shard scaled by fl(1 / N), then the all-gather below
+        FMI_COMM_RC(c->t->reduce_scatter(op == FMI_OP_AVG ? FMI_OP_SUM : op, dtype, src, red, shard, s));
+        if (op == FMI_OP_AVG) FMI_COMM_RC(launch_mean_scale(dtype, red, shard, N, s));
     }
     if (padded == n) return c->t->all_gather(red, static_cast<char*>(recv), shard * esz, s);
     char* out = nullptr;
@@ -2081,6 +2088,7 @@ static int comm_reduce_impl(fmi_comm_t comm, int op, int dtype, int alg, const v
 // plain reduce.
 static int comm_reduce_sendbuf_impl(fmi_comm_t comm, int op, int dtype, int alg, void* send, void* recv, size_t n, int root,
                             fmi_stream_t stream) {
+    FMI_COMM_RC(refuse_avg(op, "fmi_comm_reduce_sendbuf", "the partials it leaves in the sendbufs are sums"));
     if (alg == FMI_ALG_REDUCE_LTR) return comm_reduce_impl(comm, op, dtype, alg, send, recv, n, root, stream);
     int kd = 0;  // the shard step's dtype argument (check_common)
     FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
@@ -2138,7 +2146,7 @@ static int comm_reduce_sendbuf_impl(fmi_comm_t comm, int op, int dtype, int alg,
 static int comm_scan_impl(fmi_comm_t comm, int op, int dtype, int alg, const void* send, void* recv, size_t n,
                   fmi_stream_t stream) {
     int kd = 0;  // the shard step's dtype argument (check_common)
-    FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
+    FMI_COMM_RC(check_common(comm, op, &dtype, &kd, "fmi_comm_scan", "a prefix over the ranks has no mean"));
     if (alg != FMI_ALG_SCAN && alg != FMI_ALG_SCAN_LTR) return fail(FMI_ERR_INVALID, "scan: alg must be SCAN or SCAN_LTR");
     if (n == 0) return FMI_OK;
     if (!send || !recv) return fail(FMI_ERR_INVALID, "null bucket");

@@ -883,6 +883,7 @@ bool all_aligned16(const void* const* a, void* const* b, int P) {
 }  // namespace
 
 int reduce_partials(int op, int dtype_arg, void* const* outs, const void* const* ins, int P, size_t n, hipStream_t s) {
+    FMI_RC_TRY(refuse_avg(op, "reduce partials", "the partials interior peers keep are sums"));
     if (n == 0) return FMI_OK;
     int dtype = 0;
     FMI_RC_TRY(canonical_dtype(op, dtype_arg, true, P, &dtype));
@@ -1352,12 +1353,14 @@ int fmi_graph_destroy(fmi_graph_t graph) {
 
 // ---- hot path ----------------------------------------------------------------------------------------
 int fmi_dev_reduce_pair(int op, int dtype, void* inout, const void* in, size_t n, fmi_stream_t stream) {
+    if (int rc = refuse_avg(op, "fmi_dev_reduce_pair", "a pairwise mean does not compose (run FMI_OP_SUM, then fmi_dev_mean_scale once)")) return rc;
     if (int rc = canonical_dtype(op, dtype, false, 2, &dtype)) return rc;  // one combine is one rounding: FMI_ACC_F32 dropped
     if (int rc = require_device()) return rc;
     return launch_combine(op, dtype, inout, inout, in, n, resolve(stream));
 }
 
 int fmi_dev_reduce_pair_batch(int op, int dtype, const fmi_pair_desc_t* descs, int count, fmi_stream_t stream) {
+    if (int rc = refuse_avg(op, "fmi_dev_reduce_pair_batch", "a pairwise mean does not compose (run FMI_OP_SUM, then fmi_dev_mean_scale once)")) return rc;
     if (int rc = canonical_dtype(op, dtype, false, 2, &dtype)) return rc;
     if (int rc = require_device()) return rc;
     if (op < FMI_OP_SUM || op > FMI_OP_MIN) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
@@ -1422,6 +1425,7 @@ int fmi_dev_reduce_pair_batch(int op, int dtype, const fmi_pair_desc_t* descs, i
 }
 
 int fmi_dev_combine(int op, int dtype, void* out, const void* a, const void* b, size_t n, fmi_stream_t stream) {
+    if (int rc = refuse_avg(op, "fmi_dev_combine", "a pairwise mean does not compose (run FMI_OP_SUM, then fmi_dev_mean_scale once)")) return rc;
     if (int rc = canonical_dtype(op, dtype, false, 2, &dtype)) return rc;
     if (int rc = require_device()) return rc;
     return launch_combine(op, dtype, out, a, b, n, resolve(stream));
@@ -1433,6 +1437,16 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
     if (int rc = canonical_dtype(op, dtype_arg, true, P, &dtype)) return rc;
     const bool acc = accumulates_f32(dtype);
     dtype = storage_dtype(dtype);
+    // FMI_OP_AVG: the SUM program, its result scaled by fl(1 / P) before the one store (include/fmi_dev.h). From here
+    // on `op` is the program's op; P = 1 stays the copy.
+    const bool avg = op == FMI_OP_AVG && P != 1;
+    if (op == FMI_OP_AVG) {
+        if (alg == FMI_ALG_SCAN || alg == FMI_ALG_SCAN_LTR)
+            return refuse_avg(op, "fmi_dev_reduce_tree", "a scan algorithm's prefixes have no mean");
+        if (dtype_size(dtype) != 0 && !is_float(dtype))
+            return refuse_avg(op, "fmi_dev_reduce_tree", ("dtype " + std::to_string(dtype) + " is an integer dtype").c_str());
+        op = FMI_OP_SUM;
+    }
     if (int rc = check_peer_args(op, dtype, P)) return rc;
     if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
         return fail(FMI_ERR_INVALID, "fmi_dev_reduce_tree: alg must be ALLREDUCE, REDUCE or REDUCE_LTR");
@@ -1453,11 +1467,18 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
         // the inner call applies the root's rotation itself: the temporaries keep the caller's order
         const int slot = P;  // the result in a temporary of its own
         void* outs[1] = {out};
+        // a mean scales the f32 result temporary (the inner FMI_F32 mean) before it is narrowed: one rounding to storage
         return acc32_fallback(dtype, outs, &slot, 1, ins, P, P + 1, n, s, [&](void* const* fo, const void* const* fi) {
-            return reduce_tree_impl(op, FMI_F32, alg, fo[0], fi, P, rank, n, stream);
+            return reduce_tree_impl(avg ? FMI_OP_AVG : op, FMI_F32, alg, fo[0], fi, P, rank, n, stream);
         });
     }
+    if (avg && (P > sched::kMaxFusedPeers || !aligned)) {
+        // beyond the fused mean kernels: the unchanged SUM program, then the scale kernel in place on its result
+        if (int rc = reduce_tree_impl(FMI_OP_SUM, dtype, alg, out, ins, P, rank, n, stream)) return rc;
+        return launch_mean_scale(dtype, out, n, P, s);
+    }
     if (acc) dtype |= FMI_ACC_F32;  // launch_fused hands these to the acc32 units
+    if (avg) op = FMI_OP_AVG;       // and these to the mean units: 2 <= P <= 16, aligned
     if (P >= 2 && aligned && fused_covers(op, storage_dtype(dtype), alg, P)) {
         if (P > sched::max_fused_peers(alg)) return run_tree_blocked(op, dtype, alg, out, order.data(), P, rank, n, s);
         PeerPtrs ptrs{};
@@ -1478,6 +1499,7 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
 
 static int scan_peers_impl(int op, int dtype_arg, int alg, void* const* outs, const void* const* ins, int P, size_t n,
                            fmi_stream_t stream) {
+    if (int rc = refuse_avg(op, "fmi_dev_scan_peers", "a prefix over the peers has no mean")) return rc;
     int dtype = 0;  // as in reduce_tree_impl
     if (int rc = canonical_dtype(op, dtype_arg, true, P, &dtype)) return rc;
     const bool acc = accumulates_f32(dtype);
@@ -1522,6 +1544,7 @@ static int scan_peers_impl(int op, int dtype_arg, int alg, void* const* outs, co
 // keeps a slot's staging from being overwritten before its previous D2H finished, while the other slot's
 // H2D overlaps this slot's kernel + D2H.
 int fmi_host_reduce_pair(int op, int dtype, void* inout, const void* in, size_t n) {
+    if (int rc = refuse_avg(op, "fmi_host_reduce_pair", "a pairwise mean does not compose (run FMI_OP_SUM, then fmi_dev_mean_scale once)")) return rc;
     if (int rc = canonical_dtype(op, dtype, false, 2, &dtype)) return rc;
     if (op < FMI_OP_SUM || op > FMI_OP_MIN) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
     const size_t esz = dtype_size(dtype);
@@ -1641,6 +1664,20 @@ static int schedule_expr_impl(int alg, int P, int rank, char* buf, size_t len) {
 int fmi_dev_reduce_tree(int op, int dtype, int alg, void* out, const void* const* ins, int P, int rank, size_t n,
                         fmi_stream_t stream) {
     return guarded("fmi_dev_reduce_tree", [&] { return reduce_tree_impl(op, dtype, alg, out, ins, P, rank, n, stream); });
+}
+
+int fmi_dev_mean_scale(int dtype, void* inout, size_t n, int P, fmi_stream_t stream) {
+    return guarded("fmi_dev_mean_scale", [&]() -> int {
+        if (dtype_size(dtype) == 0) return fail(FMI_ERR_INVALID, "fmi_dev_mean_scale: unknown dtype " + std::to_string(dtype));
+        if (!is_float(dtype))
+            return fail(FMI_ERR_INVALID, "fmi_dev_mean_scale: dtype " + std::to_string(dtype) + " is an integer dtype; the mean "
+                                         "(FMI_OP_AVG) is defined for float buckets");
+        if (P < 1) return fail(FMI_ERR_INVALID, "fmi_dev_mean_scale: P must be >= 1, got " + std::to_string(P));
+        if (n == 0) return FMI_OK;
+        if (!inout) return fail(FMI_ERR_INVALID, "null buffer");
+        if (int rc = require_device()) return rc;
+        return launch_mean_scale(dtype, inout, n, P, resolve(stream));
+    });
 }
 
 int fmi_dev_scan_peers(int op, int dtype, int alg, void* const* outs, const void* const* ins, int P, size_t n,

@@ -1,0 +1,9 @@
+// FMI_OP_AVG, P = 2..16: the fused kernels of reduce_ltr at op OpAvg, for f32, f64, f16, bf16 and the two 16-bit floats
+// with f32 values (FMI_ACC_F32). The SUM program with the stored value scaled by fl(1 / P): one launch, P reads, one store.
+#include "fmi_fused_impl.h"
+
+namespace fmi::dev {
+int launch_fused_avg_reduce_ltr(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
+    return launch_fused_avg_family<sched::kReduceLtr>(dtype, P, ptrs, n, s);
+}
+}  // namespace fmi::dev

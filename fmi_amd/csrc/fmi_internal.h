@@ -62,8 +62,16 @@ inline int canonical_dtype(int op, int dtype_arg, bool pway, int P, int* canon) 
     if (!is_half_dtype(*canon))
         return fail(FMI_ERR_INVALID, "dtype " + std::to_string(dtype_arg) + ": FMI_ACC_F32 is valid only as FMI_F16 | FMI_ACC_F32 "
                                      "or FMI_BF16 | FMI_ACC_F32");
-    if (pway && P != 1 && (op == FMI_OP_SUM || op == FMI_OP_PROD)) *canon |= FMI_ACC_F32;
+    if (pway && P != 1 && (op == FMI_OP_SUM || op == FMI_OP_PROD || op == FMI_OP_AVG)) *canon |= FMI_ACC_F32;
     return FMI_OK;
+}
+
+// FMI_OP_AVG (include/fmi_dev.h) is valid only where a call produces a reduction result over float buckets. The entry
+// points that cannot take it refuse it first of all, before any other check and before a device is needed:
+// `who` names the entry point, `why` the reason.
+inline int refuse_avg(int op, const char* who, const char* why) {
+    if (op != FMI_OP_AVG) return FMI_OK;
+    return fail(FMI_ERR_INVALID, std::string(who) + ": op " + std::to_string(op) + " (FMI_OP_AVG) is not valid here: " + why);
 }
 
 // Which (op, dtype, algorithm, P) have a single-pass kernel (fused, or built from fused blocks): the core dtypes and
@@ -183,6 +191,16 @@ int launch_fused_acc32_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs
 int launch_fused_acc32_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_acc32_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_acc32_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+// FMI_OP_AVG at 2 <= P <= 16 (alg: one of the three reduce algorithms; dtype: a float storage dtype, with FMI_ACC_F32
+// where the values are f32): launch_fused hands these to launch_fused_avg (fmi_fused_avg.hip), which picks the
+// algorithm's translation unit (fmi_fused_avg_*.hip).
+int launch_fused_avg(int alg, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_avg_allreduce(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_avg_reduce(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_avg_reduce_ltr(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+// The mean's scale step alone (fmi_scale.hip), in place, any alignment: inout[i] = store(fl_V(value(inout[i]) * fl_V(1 / P))).
+// dtype: one of the four float dtypes.
+int launch_mean_scale(int dtype, void* inout, size_t n, int P, hipStream_t s);
 // The fallback's streaming conversions (fmi_acc32_convert.hip), any alignment: dst[i] = (float)src[i] (exact) and
 // dst[i] = the storage type's rounding of src[i]. dtype: FMI_F16 or FMI_BF16.
 int launch_widen_f32(int dtype, float* dst, const void* src, size_t n, hipStream_t s);

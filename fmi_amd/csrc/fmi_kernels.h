@@ -106,6 +106,21 @@ struct OpMin {
         return (b < a) ? b : a;
     }
 };
+// FMI_OP_AVG (include/fmi_dev.h): the mean over the P peers of a fused tree program. Its steps are OpSum's (StepOp), so
+// every combine is the SUM program's; `finish` then scales the one value a thread is about to store by r_P = fl_V(1 / P),
+// a constant of the instantiation, in the value type V (f32 for the 16-bit floats, plain or Acc32) and narrows once:
+// out = store(fl_V(S * r_P)). Only the tree kernels know it: no pairwise, scan or with_op_dtype instantiation exists.
+struct OpAvg : OpSum {};
+template <class Op>
+inline constexpr bool is_avg_v = std::is_same_v<Op, OpAvg>;
+template <class Op>
+struct StepOp {
+    using type = Op;
+};
+template <>
+struct StepOp<OpAvg> {
+    using type = OpSum;
+};
 
 // ---------------------------------------------------------------------------------------------------
 // 16-byte lane groups and their loads/stores.
@@ -343,6 +358,32 @@ __device__ __forceinline__ Lanes<T, W> to_storage(const Lanes<V, W>& x) {
             }
         }
         return r;
+    }
+}
+
+// OpAvg's last step: the value a tree kernel is about to store, times r_P, as storage lanes. f32 / f64: one IEEE multiply
+// in the element type. 16-bit floats: the value in f32 (widened, exact, where the program keeps 16-bit values), one f32
+// multiply, and the narrowing Op::apply ends with, from an opaque register in every lane-group width: the compiler
+// otherwise fuses multiply and narrowing into v_fma_mixlo_f16 x, y, +0 (to_storage above), and -0 * r comes out as +0.
+template <class T, int P, class V, int W>
+__device__ __forceinline__ Lanes<T, W> finish_avg(const Lanes<V, W>& x) {
+    if constexpr (is_half_float_v<T>) {
+        constexpr float r = 1.0f / static_cast<float>(P);
+        Lanes<float, W> f = to_value<float>(x);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            float y = f.v[k] * r;
+            asm("" : "+v"(y));
+            f.v[k] = y;
+        }
+        return to_storage<T>(f);
+    } else {
+        static_assert(std::is_same_v<V, T> && (std::is_same_v<T, float> || std::is_same_v<T, double>), "mean of float elements");
+        constexpr T r = static_cast<T>(1) / static_cast<T>(P);
+        Lanes<T, W> y;
+#pragma unroll
+        for (int k = 0; k < W; ++k) y.v[k] = x.v[k] * r;
+        return y;
     }
 }
 
@@ -604,13 +645,15 @@ template <class Op, class T, int ALG, int P, bool ALL_RANKS, int W, class V = T>
 __device__ __forceinline__ void tree_group(const PeerPtrs& ptrs, int rank, size_t elem) {
     Lanes<V, W> v[P + kNumSteps<ALG, P>];
     load_peers<T, W, P>(v, ptrs, elem, std::make_index_sequence<P>{});
-    run_steps<Op, V, W, ALG, P, kRewidenFused<V, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
+    run_steps<typename StepOp<Op>::type, V, W, ALG, P, kRewidenFused<V, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
     Lanes<V, W> r;
     if constexpr (ALL_RANKS)
         r = pick_rank<V, W, ALG, P>(v, rank, std::make_index_sequence<P>{});
     else
         r = v[kOut<ALG, P, 0>];
-    if constexpr (std::is_same_v<V, T>)
+    if constexpr (is_avg_v<Op>)
+        store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[0]) + elem, finish_avg<T, P>(r));
+    else if constexpr (std::is_same_v<V, T>)
         store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[0]) + elem, r);
     else
         store_lanes<kFusedNT, T, W>(static_cast<T*>(ptrs.out[0]) + elem, to_storage<T>(r));
@@ -620,13 +663,15 @@ template <class Op, class T, int ALG, int P, bool ALL_RANKS, int W, class V = T>
 __device__ __forceinline__ void tree_group_tile(const PeerPtrs& ptrs, int rank, size_t tile_byte, unsigned lane_byte) {
     Lanes<V, W> v[P + kNumSteps<ALG, P>];
     load_peers_tile<T, W, P>(v, ptrs, tile_byte, lane_byte, std::make_index_sequence<P>{});
-    run_steps<Op, V, W, ALG, P, kRewidenFused<V, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
+    run_steps<typename StepOp<Op>::type, V, W, ALG, P, kRewidenFused<V, ALL_RANKS, P>>(v, std::make_index_sequence<kNumSteps<ALG, P>>{});
     Lanes<V, W> r;
     if constexpr (ALL_RANKS)
         r = pick_rank<V, W, ALG, P>(v, rank, std::make_index_sequence<P>{});
     else
         r = v[kOut<ALG, P, 0>];
-    if constexpr (std::is_same_v<V, T>)
+    if constexpr (is_avg_v<Op>)
+        store_tile<kTreeStoreAux, T, W>(ptrs.out[0], tile_byte, lane_byte, finish_avg<T, P>(r));
+    else if constexpr (std::is_same_v<V, T>)
         store_tile<kTreeStoreAux, T, W>(ptrs.out[0], tile_byte, lane_byte, r);
     else
         store_tile<kTreeStoreAux, T, W>(ptrs.out[0], tile_byte, lane_byte, to_storage<T>(r));

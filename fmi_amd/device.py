@@ -17,11 +17,15 @@ from . import _lib
 
 
 class Op(enum.IntEnum):
-    """Reference Python op enum SUM/PROD/MAX/MIN (reference python/PythonCommunicator.h:13-15)."""
+    """Reference Python op enum SUM/PROD/MAX/MIN (reference python/PythonCommunicator.h:13-15), and AVG, the mean
+    over the peers (fmi_dev.h's FMI_OP_AVG; 4 is the reference's CUSTOM and stays unassigned): the SUM program's
+    value times the rounded reciprocal of the peer count, float dtypes, in the calls that produce a reduction result
+    (reduce_tree, comm.allreduce / reduce / allreduce_host)."""
     SUM = 0
     PROD = 1
     MAX = 2
     MIN = 3
+    AVG = 5
 
 
 class DType(enum.IntEnum):
@@ -376,6 +380,15 @@ def reduce_tree(op: Op, alg: Alg, out: Bucket, ins: Sequence[Bucket], rank: int 
     _check_peers(out, ins)
     _lib.call("fmi_dev_reduce_tree", int(op), dtype, int(alg), out.ptr, _ptr_array(ins), len(ins), rank,
               out.n, _sptr(stream))
+
+
+def mean_scale(inout: Bucket, P: int, n: Optional[int] = None, stream=None) -> None:
+    """inout = inout * fl(1 / P) in place (fmi_dev_mean_scale): Op.AVG's last step alone, for a SUM that went through
+    an exchange of the caller's own. Float buckets; f16 / bf16 multiply in f32 and round to storage once."""
+    n = inout.n if n is None else n
+    if inout.n < n:
+        raise ValueError("mean_scale: the bucket must hold n elements")
+    _lib.call("fmi_dev_mean_scale", int(inout.dtype), inout.ptr, n, int(P), _sptr(stream))
 
 
 def scan_peers(op: Op, alg: Alg, outs: Sequence[Bucket], ins: Sequence[Bucket], stream=None,

@@ -55,6 +55,7 @@ class op(enum.IntEnum):  # noqa: N801 - reference spelling (python/fmi_python.cp
     max = 2
     min = 3
     custom = 4
+    avg = 5  # the mean over the peers (fmi_dev.h's FMI_OP_AVG): double / double_list, reduce and allreduce
 
 
 class hints(enum.IntEnum):  # noqa: N801
@@ -263,7 +264,17 @@ class Communicator:
         res = _eval_expr(expr, [v[0].item() for v in values], f.fn)
         return _NP[t.type](res).item()
 
+    @staticmethod
+    def _check_avg(f: func, t: types, what: str) -> None:
+        if f.op != op.avg:
+            return
+        if what == "scan":
+            raise ValueError("fmi.op.avg: a scan's prefixes have no mean; use reduce or allreduce")
+        if t.type not in (datatypes.double, datatypes.double_list):
+            raise ValueError(f"fmi.op.avg needs double or double_list data, got {t.type.name}")
+
     def reduce(self, data, root: int, f: func, t: types):
+        self._check_avg(f, t, "reduce")
         mine = self._array(data, t)
         comm_, assoc = self._flags(f, t)
         ordered = not (comm_ and assoc)
@@ -284,6 +295,7 @@ class Communicator:
         return self._py(recv.numpy(), t) if recv is not None else self._py(np.zeros_like(mine), t)
 
     def allreduce(self, data, f: func, t: types):
+        self._check_avg(f, t, "allreduce")
         mine = self._array(data, t)
         comm_, assoc = self._flags(f, t)
         ordered = not (comm_ and assoc)
@@ -297,6 +309,7 @@ class Communicator:
         return self._py(recv, t)
 
     def scan(self, data, f: func, t: types):
+        self._check_avg(f, t, "scan")
         mine = self._array(data, t)
         comm_, assoc = self._flags(f, t)
         ordered = not (comm_ and assoc)

@@ -56,7 +56,38 @@ typedef enum {
 
 /* ---- op / dtype / algorithm descriptors -------------------------------------------------------- */
 /* Op ids mirror the reference Python enum SUM/PROD/MAX/MIN (reference python/PythonCommunicator.h:13-15). */
-typedef enum { FMI_OP_SUM = 0, FMI_OP_PROD = 1, FMI_OP_MAX = 2, FMI_OP_MIN = 3 } fmi_op_t;
+typedef enum { FMI_OP_SUM = 0, FMI_OP_PROD = 1, FMI_OP_MAX = 2, FMI_OP_MIN = 3, FMI_OP_AVG = 5 } fmi_op_t;
+/* FMI_OP_AVG = 5: the mean over the peers. Id 4 stays unassigned in the C-ABI: the reference's Python enum gives 4
+ * to CUSTOM. Additive: fmi_abi_version() stays 1. A call with FMI_OP_AVG over P peers stores
+ *     out = store( fl_V( S x r_P ) )
+ *   V    the value type: f32 for FMI_F32, FMI_F16 and FMI_BF16 (with or without FMI_ACC_F32); f64 for FMI_F64.
+ *   S    what the same call with FMI_OP_SUM and the same `alg` holds in V just before its store. Plain dtypes: S is
+ *        the SUM result itself (for f16 / bf16 already rounded to storage after every combine; it is widened).
+ *        With FMI_ACC_F32: S is the f32 program value, not yet narrowed, so the result is
+ *        narrow(F32sum(widen(x)) x r_P), one rounding to storage in all.
+ *   r_P  fl_V(1 / P), the correctly rounded reciprocal in V. The product is one IEEE multiply (round-to-nearest-even,
+ *        subnormals kept, no contraction).
+ *   store  identity for f32 / f64; for the 16-bit types the narrowing every combine ends with.
+ * Multiplying by the reciprocal, not dividing, is deliberate: it is what RCCL's own average does, it costs one VALU
+ * op per element, and it equals S / P exactly for P = 2^k, the usual GPU counts. For other P it differs from the
+ * division in the last bit on some elements (about a third of random f32 sums at P = 3). P = 1 stays the copy, bits
+ * unchanged. A NaN result is some NaN.
+ * Valid: float dtypes only, and only in calls that produce a reduction result:
+ *   fmi_dev_reduce_tree at FMI_ALG_ALLREDUCE / _REDUCE / _REDUCE_LTR                 divisor P
+ *   fmi_comm_allreduce on every path, fmi_comm_allreduce_host, fmi_comm_reduce        divisor nranks
+ *     (the shard step is the fmi_dev_reduce_tree call above with P = nranks; FMI_PATH_RCCL runs its reduce-scatter
+ *     with SUM, scales its shard, then all-gathers: no new RCCL call, and its bound is the SUM bound times r_P plus
+ *     one ulp of the result; a one-rank communicator stays the copy)
+ * FMI_ERR_INVALID, with a message naming the op and the reason:
+ *   integer dtypes;
+ *   fmi_dev_reduce_pair, _batch, fmi_dev_combine, fmi_host_reduce_pair (a pairwise mean does not compose);
+ *   fmi_dev_scan_peers, fmi_comm_scan, and the scan algorithms passed to fmi_dev_reduce_tree (a prefix has no mean);
+ *   fmi_comm_reduce_sendbuf (the partials it leaves in the sendbufs are sums).
+ * At 2 <= P <= 16 on 16-B aligned buckets the call is ONE fused kernel (P reads, one store): the SUM program with the
+ * value scaled in registers just before its store. Every other call (P > 16, unaligned buckets) runs the unchanged SUM
+ * program and then the scale kernel of fmi_dev_mean_scale in place on `out`: the same bits by the definition above.
+ * With FMI_ACC_F32 beyond 16 peers or on unaligned buckets the f32 result temporary is scaled before it is narrowed:
+ * still one rounding to storage. */
 /* Element types. The reference's buckets are Data<std::vector<A>> for any fundamental A
  * (include/comm/Data.h:50-73); f32 / f64 / i32 / i64 run every kernel, including the fused P-way ones.
  * The other integer widths run the pairwise kernel, and their P-way programs run as pairwise passes in
@@ -201,7 +232,10 @@ int fmi_event_elapsed_ms(float* ms, fmi_event_t start, fmi_event_t stop);
  * fmi_dev_combine, the d2d / memset copies, and fmi_dev_reduce_tree / fmi_dev_scan_peers up to 16 peers
  * (one fused kernel each) on 16-B aligned f32 / f64 / i32 / i64 / f16 / bf16 buckets, at every algorithm: for
  * FMI_F16 / FMI_BF16 that includes FMI_ALG_REDUCE_LTR and FMI_ALG_SCAN_LTR. FMI_ACC_F32 calls at P <= 16 on aligned buckets are capture-safe (one fused
- * kernel each); beyond 16 peers or on unaligned buckets they need the f32 temporaries and are not. Beyond 16 peers a call on such buckets
+ * kernel each); beyond 16 peers or on unaligned buckets they need the f32 temporaries and are not. FMI_OP_AVG at
+ * P <= 16 on aligned buckets is capture-safe (one fused kernel); beyond that it is capture-safe exactly where the
+ * FMI_OP_SUM call is (the scale runs in place and needs no temporary), and with FMI_ACC_F32 beyond 16 peers or on
+ * unaligned buckets it is not. fmi_dev_mean_scale is capture-safe. Beyond 16 peers a call on such buckets
  * is capture-safe exactly where it needs no temporary bucket, which at FMI_TUNE_BLOCKS_ONE_PASS = 1 (the default)
  * is, the same for the six dtypes: FMI_ALG_ALLREDUCE at P <= 31 and P = 32, 48, 64, 80, 96, 112; FMI_ALG_REDUCE at
  * P <= 128; FMI_ALG_SCAN at P <= 143; FMI_ALG_SCAN_LTR at any P; FMI_ALG_REDUCE_LTR at P <= 128, and beyond when
@@ -253,6 +287,13 @@ int fmi_dev_combine(int op, int dtype, void* out, const void* a, const void* b, 
  * integers run the same order as pairwise passes. */
 int fmi_dev_reduce_tree(int op, int dtype, int alg, void* out, const void* const* ins, int P, int rank,
                         size_t n, fmi_stream_t stream);
+
+/* The scale step of FMI_OP_AVG alone, in place: inout[i] = store(fl_V(value(inout[i]) x r_P)), r_P = fl_V(1 / P), as
+ * defined at FMI_OP_AVG, for callers who ran FMI_OP_SUM through an exchange of their own. dtype: FMI_F32, FMI_F64,
+ * FMI_F16 or FMI_BF16 (anything else, FMI_ACC_F32 included: FMI_ERR_INVALID); P >= 1 (P = 1 leaves the bits
+ * unchanged); any alignment (16-B nontemporal accesses on a 16-B aligned bucket, one element per thread otherwise);
+ * n = 0 succeeds. One launch, graph-capturable. */
+int fmi_dev_mean_scale(int dtype, void* inout, size_t n, int P, fmi_stream_t stream);
 
 /* Peer-axis inclusive scan of P device buckets: outs[k] = x0 (+) ... (+) xk with the evaluation order
  * of `alg` (FMI_ALG_SCAN or FMI_ALG_SCAN_LTR). Replaces reference PeerToPeer::scan_no_order / scan_ltr

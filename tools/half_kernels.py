@@ -26,6 +26,18 @@ shape (same bytes) and the f32 kernel of equal bytes, sum, for bf16 and f16:
 
 Each line carries its own spread over the three passes, its ratio to the plain 16-bit kernel and to f32 per pass.
 
+With --avg, the mean (FMI_OP_AVG) beside SUM of the same shape run by ANOTHER build of the library (--yardstick-lib,
+e.g. the parent commit's libfmi_dev.so), both loaded into this process and interleaved in the same passes over the
+same buckets:
+
+  allreduce8    ALLREDUCE over 8 peers: f32, bf16, bf16 acc32    (9 x 256 MiB per launch; 3 groups)  one fused kernel
+  allreduce16   ALLREDUCE over 16 peers: f32, bf16, bf16 acc32   (17 x 256 MiB; 2 groups)            one fused kernel
+  allreduce17   ALLREDUCE over 17 peers: f32                     (18 x 256 MiB; 2 groups)  the SUM kernel, then the
+                scale kernel: (P + 3) / (P + 1) of the SUM's traffic; reported beside that estimate, no bar
+
+Each line carries the yardstick's rate per pass, the ratio per pass and the yardstick f32 SUM kernel's own spread
+over the three passes: a fused row more than that spread below its yardstick is a finding.
+
 The yardstick of a 16-bit kernel is the f32 kernel of the same family and op. The same rows run against any
 library (FMI_DEV_LIB), e.g. one built from an earlier commit whose 16-bit programs ran as pairwise passes.
 
@@ -37,6 +49,7 @@ than that spread below f32 is a finding.
 
     python3 tools/half_kernels.py [--out profiles/NAME.jsonl]
     python3 tools/half_kernels.py --acc32 [--only allreduce8,scan16] [--out profiles/NAME.jsonl]
+    python3 tools/half_kernels.py --avg --yardstick-lib PATH/libfmi_dev.so [--out profiles/avg.jsonl]
     python3 tools/half_kernels.py --forms [--only reduce_ltr8,reduce32] [--label NAME] [--out profiles/NAME.jsonl]
 """
 import argparse
@@ -203,6 +216,112 @@ def acc32(args):
         fmi_amd.sync()
 
 
+class RawLib:
+    """A build of libfmi_dev.so driven through its C-ABI alone (the yardstick library: its own state and stream next to
+    the package's library in one process; device pointers are the process's, so both work on the same buckets)."""
+
+    def __init__(self, path):
+        import ctypes
+        from fmi_amd import _lib
+        self.c = ctypes
+        self.lib = ctypes.CDLL(path)
+        for name in ("fmi_dev_init", "fmi_dev_reduce_tree", "fmi_event_create", "fmi_event_destroy", "fmi_event_record",
+                     "fmi_event_sync", "fmi_event_elapsed_ms", "fmi_dev_sync", "fmi_last_error"):
+            fn = getattr(self.lib, name)
+            fn.restype, fn.argtypes = _lib.SIGNATURES[name] if name in _lib.SIGNATURES else (ctypes.c_char_p, [])
+        self.call("fmi_dev_init", 0)
+
+    def call(self, name, *args):
+        rc = getattr(self.lib, name)(*args)
+        if rc != 0:
+            raise RuntimeError(f"{name}: {rc} {self.lib.fmi_last_error().decode()}")
+
+    def reduce_tree(self, op, dtype, alg, out, ins, n):
+        ptrs = (self.c.c_void_p * len(ins))(*[b.ptr for b in ins])
+        self.call("fmi_dev_reduce_tree", int(op), int(dtype), int(alg), out.ptr, ptrs, len(ins), 0, n, None)
+
+    def timed(self, launch, iters, warm):
+        for k in range(warm):
+            launch(k)
+        e0, e1, ms = self.c.c_void_p(), self.c.c_void_p(), self.c.c_float()
+        self.call("fmi_event_create", self.c.byref(e0))
+        self.call("fmi_event_create", self.c.byref(e1))
+        self.call("fmi_event_record", e0, None)
+        for k in range(warm, warm + iters):
+            launch(k)
+        self.call("fmi_event_record", e1, None)
+        self.call("fmi_event_sync", e1)
+        self.call("fmi_event_elapsed_ms", self.c.byref(ms), e0, e1)
+        self.call("fmi_event_destroy", e0)
+        self.call("fmi_event_destroy", e1)
+        return ms.value / iters
+
+
+# family: (peers, rotating groups, rows (dtype, accumulate_f32))
+AVG = {
+    "allreduce8": (8, 3, [("f32", False), ("bf16", False), ("bf16", True)]),
+    "allreduce16": (16, 2, [("f32", False), ("bf16", False), ("bf16", True)]),
+    "allreduce17": (17, 2, [("f32", False)]),
+}
+
+
+def avg(args):
+    if not args.yardstick_lib:
+        sys.exit("--avg needs --yardstick-lib: the build of libfmi_dev.so whose SUM is the yardstick")
+    yard = RawLib(os.path.abspath(args.yardstick_lib))
+    nbytes = args.mib * MIB
+    spread = lambda xs: round((max(xs) - min(xs)) / statistics.median(xs), 4)  # noqa: E731
+    for fam in (args.only.split(",") if args.only else list(AVG)):
+        P, sets, rows = AVG[fam]
+        count = P + 1
+        groups = {}
+        for name in {r[0] for r in rows}:
+            dt, esz = DTYPES[name]
+            groups[name] = [Bucket.group(count, nbytes // esz, dt) for _ in range(sets)]
+            for g in groups[name]:
+                for p in range(P):
+                    g[p].fill_synthetic(11, p)
+        fmi_amd.sync()
+        mine, base = {r: [] for r in rows}, {r: [] for r in rows}
+        for _ in range(PASSES):
+            for name, acc in rows:
+                gs = groups[name]
+                dtype = fmi_amd.device.acc_dtype(gs[0][0].dtype, acc)
+                ms = timed(lambda k: fmi_amd.reduce_tree(Op.AVG, Alg.ALLREDUCE, gs[k % sets][P], gs[k % sets][:P],
+                                                         accumulate_f32=acc), args.iters, sets)
+                mine[(name, acc)].append(count * nbytes / (ms * 1e-3))
+                fmi_amd.sync()
+                ms = yard.timed(lambda k: yard.reduce_tree(Op.SUM, dtype, Alg.ALLREDUCE, gs[k % sets][P], gs[k % sets][:P],
+                                                           gs[0][0].n), args.iters, sets)
+                base[(name, acc)].append(count * nbytes / (ms * 1e-3))
+                yard.call("fmi_dev_sync")
+        lines = []
+        for name, acc in rows:
+            m, y = mine[(name, acc)], base[(name, acc)]
+            line = {"tool": "tools/half_kernels.py --avg", "label": args.label,
+                    "kernel": f"{fam} {name}{' acc32' if acc else ''} avg", "peers": P, "bucket_mib": args.mib,
+                    "algorithmic_bytes": count * nbytes, "iters_per_pass": args.iters, "passes": PASSES,
+                    "rotating_sets": sets, "GB_s_per_pass": [round(r / 1e9, 1) for r in m],
+                    "GB_s": round(statistics.median(m) / 1e9, 1), "spread": spread(m),
+                    "yardstick": "SUM of the same shape by the yardstick library, same buckets, same passes",
+                    "yardstick_GB_s_per_pass": [round(r / 1e9, 1) for r in y],
+                    "yardstick_GB_s": round(statistics.median(y) / 1e9, 1), "yardstick_spread": spread(y),
+                    "ratio_to_yardstick_per_pass": [round(a / b, 4) for a, b in zip(m, y)],
+                    "ratio_to_yardstick": round(statistics.median([a / b for a, b in zip(m, y)]), 4),
+                    "yardstick_f32_spread": spread(base[("f32", False)]),
+                    "timing": "two HIP events of the launching library around back-to-back launches on its stream"}
+            if P > 16:  # SUM kernel + scale kernel: the rates count the SUM's algorithmic bytes for both
+                line["launches"] = "the SUM kernel, then the scale kernel in place"
+                line["traffic_estimate_ratio"] = round((P + 1) / (P + 3), 4)
+            lines.append(line)
+        emit(lines, args.out)
+        for gs in groups.values():
+            for g in gs:
+                for b in g:
+                    b.free()
+        fmi_amd.sync()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256, help="bytes per bucket")
@@ -212,10 +331,15 @@ def main():
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--forms", action="store_true", help="the fused forms (see above) instead of pair / tree8")
     ap.add_argument("--acc32", action="store_true", help="FMI_ACC_F32 beside the plain 16-bit and the f32 kernels")
-    ap.add_argument("--only", default=None, help="with --forms / --acc32: a comma-separated subset of the families")
+    ap.add_argument("--avg", action="store_true", help="FMI_OP_AVG beside SUM of the same shape by --yardstick-lib")
+    ap.add_argument("--yardstick-lib", default=os.environ.get("FMI_DEV_YARDSTICK_LIB"),
+                    help="with --avg: another build of libfmi_dev.so (e.g. the parent commit's) whose SUM is the yardstick")
+    ap.add_argument("--only", default=None, help="with --forms / --acc32 / --avg: a comma-separated subset of the families")
     ap.add_argument("--label", default="tree", help="with --forms: what the lines are tagged with (e.g. the commit)")
     args = ap.parse_args()
     fmi_amd.init(0)
+    if args.avg:
+        return avg(args)
     if args.acc32:
         return acc32(args)
     if args.forms:

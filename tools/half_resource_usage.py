@@ -8,6 +8,7 @@ and every kernel's VGPRs / AGPRs / scratch / occupancy are collected. Exits 1 if
     python3 tools/half_resource_usage.py --logs DIR      # parse remark logs kept from a build instead
     python3 tools/half_resource_usage.py --core          # the f32 kernels of the core units, for the comparison
     python3 tools/half_resource_usage.py --acc32         # the FMI_ACC_F32 units alone
+    python3 tools/half_resource_usage.py --avg           # the FMI_OP_AVG units (fmi_fused_avg_*.hip, fmi_scale.hip), every dtype
 
 The summary groups kernels by family, dtype and op and gives the range over P.
 """
@@ -59,6 +60,9 @@ DTYPES = {"DF16_": "f16", "DF16b": "bf16", "f": "f32", "d": "f64", "i": "i32", "
 def describe(mangled):
     """(kernel, dtype, op, the remaining template arguments) from a kernel's Itanium-mangled name, e.g.
     _ZN3fmi3dev11tree_kernelINS0_5OpSumEDF16_Li7ELi32ELb0EEEv...: tree_kernel<OpSum, _Float16, 7, 32, false>."""
+    m = re.search(r"(?<=\d)(scale_kernel)I(DF16_|DF16b|[fd])E", mangled)
+    if m:  # fmi_scale.hip: one kernel per float dtype
+        return m.group(1), DTYPES[m.group(2)], "", ""
     m = re.search(r"(?<=\d)([a-z_]+_kernel)INS\d*_\d(Op[A-Z][a-z]+)E(NS\d*_5Acc32I)?(DF16_|DF16b|[fdil])(?(3)EE)((?:L[ib]\d+E)*)E",
                   mangled)
     if not m:
@@ -75,6 +79,7 @@ def main():
     ap.add_argument("--logs", help="directory of remark logs (one per unit) to parse instead of compiling")
     ap.add_argument("--core", action="store_true", help="the core units' f32 kernels instead of the half units")
     ap.add_argument("--acc32", action="store_true", help="the FMI_ACC_F32 units alone")
+    ap.add_argument("--avg", action="store_true", help="the FMI_OP_AVG units alone, every dtype")
     ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 8))
     ap.add_argument("--all", action="store_true", help="print every kernel, not the summary")
     a = ap.parse_args()
@@ -83,14 +88,15 @@ def main():
     else:
         units = lambda pat: sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, pat)))  # noqa: E731
         acc32 = units("fmi_fused_acc32_*.hip") + ["fmi_acc32_convert.hip"]
-        srcs = CORE if a.core else acc32 if a.acc32 else units("fmi_fused_half_*.hip") + acc32
+        avg = units("fmi_fused_avg_*.hip") + ["fmi_scale.hip"]
+        srcs = CORE if a.core else acc32 if a.acc32 else avg if a.avg else units("fmi_fused_half_*.hip") + acc32
         with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
             texts = list(ex.map(remarks, srcs))
     kernels = [k for t in texts for k in parse(t)]
     groups = collections.defaultdict(list)
     for k in kernels:
         d = describe(k["name"])
-        if d is None or (a.core and d[1] != "f32") or (not a.core and d[1] not in ("f16", "bf16")):
+        if d is None or (a.core and d[1] != "f32") or (not a.core and not a.avg and d[1] not in ("f16", "bf16")):
             continue
         kern, dtype, op, detail = d
         if a.all:
