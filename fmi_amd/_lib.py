@@ -96,6 +96,7 @@ SIGNATURES = {
     "fmi_dev_reduce_tree": (_i, [_i, _i, _i, _vp, _c.POINTER(_vp), _i, _i, _sz, _vp]),
     "fmi_dev_scan_peers": (_i, [_i, _i, _i, _c.POINTER(_vp), _c.POINTER(_vp), _i, _sz, _vp]),
     "fmi_dev_mean_scale": (_i, [_i, _vp, _sz, _i, _vp]),
+    "fmi_dev_convert": (_i, [_i, _vp, _i, _vp, _sz, _vp]),
     "fmi_host_reduce_pair": (_i, [_i, _i, _vp, _vp, _sz]),
     "fmi_host_device_ptr": (_i, [_vp, _sz, _c.POINTER(_vp)]),
     "fmi_host_page_locked": (_i, [_vp, _sz]),

@@ -35,6 +35,11 @@ from .device import Alg, DType, Op, acc_dtype  # noqa: E402
 _TORCH_DTYPE = {torch.float32: DType.F32, torch.float64: DType.F64, torch.int32: DType.I32, torch.int64: DType.I64,
                 torch.int8: DType.I8, torch.uint8: DType.U8, torch.int16: DType.I16, torch.float16: DType.F16,
                 torch.bfloat16: DType.BF16}
+# the two OCP 8-bit floats (a torch build without them maps nothing)
+for _name, _dt in (("float8_e4m3fn", DType.F8E4M3), ("float8_e5m2", DType.F8E5M2)):
+    if hasattr(torch, _name):
+        _TORCH_DTYPE[getattr(torch, _name)] = _dt
+_FLOAT_DTYPES = tuple(t for t, d in _TORCH_DTYPE.items() if d in (DType.F32, DType.F64, DType.F16, DType.BF16, DType.F8E4M3, DType.F8E5M2))
 _REDUCE_OP = {Op.SUM: dist.ReduceOp.SUM, Op.PROD: dist.ReduceOp.PRODUCT, Op.MAX: dist.ReduceOp.MAX,
               Op.MIN: dist.ReduceOp.MIN, Op.AVG: dist.ReduceOp.AVG}
 SHARD_ALIGN = 64  # elements: keeps every shard 256-B aligned for the 16-B vector kernels
@@ -71,7 +76,7 @@ class HipEngine:
     def reduce_tree(self, op: Op, alg: Alg, out: torch.Tensor, ins: Sequence[torch.Tensor], rank: int = 0,
                     accumulate_f32: bool = False) -> None:
         import ctypes
-        dtype = acc_dtype(_dtype(out), accumulate_f32)  # float16 / bfloat16 tensors only (FMI_ACC_F32)
+        dtype = acc_dtype(_dtype(out), accumulate_f32)  # float16 / bfloat16 / float8 tensors only (FMI_ACC_F32)
         ptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
         _lib.call("fmi_dev_reduce_tree", int(op), dtype, int(alg), out.data_ptr(), ptrs, len(ins), rank,
                   out.numel(), self._stream())
@@ -157,7 +162,7 @@ class ShardedAllreduce:
             staging = self._buf("staging", padded, x)
             dist.all_to_all_single(staging, src, group=self.group)
             parts = [staging[j * shard:(j + 1) * shard] for j in range(N)]
-            if op in (Op.MAX, Op.MIN) and x.dtype in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+            if op in (Op.MAX, Op.MIN) and x.dtype in _FLOAT_DTYPES:
                 # float max / min keep the first operand on ±0 ties and NaNs, so each GPU's peer 2g ends
                 # with its own bits: the shard owner computes the shard in every rank's order and an
                 # all-to-all (instead of the all-gather) delivers rank r's versions (same volume)

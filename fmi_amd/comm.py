@@ -115,9 +115,10 @@ class Comm:
 
     def allreduce(self, op: Op, send: Bucket, recv: Bucket, ordered: bool = False, path: Path = Path.TREE,
                   stream=None, accumulate_f32: bool = False) -> None:
-        """accumulate_f32 (F16 / BF16 buckets, here and in allreduce_host / reduce / scan): every rank's shard is
-        reduced on f32 values and rounded to the storage type once (FMI_ACC_F32); the wire stays 16-bit. Every rank
-        passes the same value. Path.RCCL has its own order and rounding and refuses it.
+        """accumulate_f32 (F16 / BF16 / F8E4M3 / F8E5M2 buckets, here and in allreduce_host / reduce / scan): every
+        rank's shard is reduced on f32 values and rounded to the storage type once (FMI_ACC_F32); the wire keeps the
+        storage type. Every rank passes the same value. Path.RCCL has its own order and rounding and refuses it, as it
+        refuses the 8-bit float dtypes altogether.
         Op.AVG (float buckets; here, in allreduce_host and in reduce): the mean over the ranks, the sum's value times
         the rounded reciprocal of the rank count before the shard's one store (FMI_OP_AVG); Path.RCCL reduce-scatters
         with SUM and scales its shard. scan and reduce(sendbuf_partials=True) refuse it."""

@@ -183,14 +183,15 @@ public:
     bool last_host_combine_on_device() const { return last_on_device_->load(); }
 
     //! The dtype argument a built-in Function's combines carry in device_op: A's fmi_dtype_t, with FMI_ACC_F32 for
-    //! Utils::Accumulate::f32 on Dev::half / Dev::bfloat16 elements; any other element type with it throws.
+    //! Utils::Accumulate::f32 on Dev::half / Dev::bfloat16 / Dev::float8_e4m3 / Dev::float8_e5m2 elements; any other
+    //! element type with it throws.
     template <typename A, typename T>
     static int device_dtype(const Utils::Function<T>& f) {
         if (f.accumulate() != Utils::Accumulate::f32) return Dev::dtype_of<A>();
-        if constexpr (std::is_same_v<A, Dev::half> || std::is_same_v<A, Dev::bfloat16>)
+        if constexpr (Dev::narrow_float_v<A>)
             return Dev::dtype_of<A>() | FMI_ACC_F32;
         else
-            throw std::runtime_error("Accumulate::f32 needs Dev::half or Dev::bfloat16 elements");
+            throw std::runtime_error("Accumulate::f32 needs Dev::half, Dev::bfloat16, Dev::float8_e4m3 or Dev::float8_e5m2 elements");
     }
 
     Utils::peer_num get_peer_id() const { return peer_id; }
@@ -234,7 +235,7 @@ private:
 
     template <typename A>
     A mean_of(A sum) const {
-        if constexpr (std::is_same_v<A, Dev::half> || std::is_same_v<A, Dev::bfloat16>)
+        if constexpr (Dev::narrow_float_v<A>)
             return A(static_cast<float>(sum) * (1.0f / static_cast<float>(num_peers)));
         else
             return sum * (static_cast<A>(1) / static_cast<A>(num_peers));

@@ -115,14 +115,102 @@ static_assert(sizeof(half) == 2 && sizeof(bfloat16) == 2 && std::is_trivially_co
                   std::is_trivially_copyable_v<bfloat16>,
               "16-bit float elements are their raw bits");
 
+// The 8-bit float element types (FMI_F8E4M3: OCP E4M3, e4m3fn; FMI_F8E5M2: OCP E5M2) as trivially copyable 1-byte
+// structs over the raw bits. Arithmetic is the C-ABI's definition (include/fmi_dev.h): widen to float (exact), operate
+// in float, narrow: round to nearest even, subnormals and the zero's sign kept, NOT saturating (a rounded magnitude
+// beyond the largest finite value, or +-inf, gives +-inf for E5M2 and NaN for E4M3; NaN stays NaN). `<` and `==`
+// compare the widened values, so std::max / std::min keep one operand's byte.
+namespace detail {
+// MANT mantissa bits, BIAS; OVER: the first magnitude (f32 bits) that no longer rounds to a finite value or, by the
+// carry out of the mantissa, to the format's own inf / NaN pattern; OVER_BYTE: what it gives.
+template <int MANT, int BIAS, std::uint32_t OVER, std::uint8_t OVER_BYTE>
+inline std::uint8_t narrow_fp8(float f) {
+    constexpr int emin = 1 - BIAS;
+    const std::uint32_t u = float_to_bits(f);
+    const std::uint32_t sign = (u >> 24) & 0x80u, mag = u & 0x7FFFFFFFu;
+    if (mag > 0x7F800000u) return static_cast<std::uint8_t>(sign | 0x7Fu);
+    if (mag >= OVER) return static_cast<std::uint8_t>(sign | OVER_BYTE);
+    const int e = static_cast<int>(mag >> 23) - 127;
+    if (e >= emin) {  // normal: drop 23 - MANT bits, round to nearest even, rebias
+        constexpr int shift = 23 - MANT;
+        const std::uint32_t r = (mag + ((1u << (shift - 1)) - 1u) + ((mag >> shift) & 1u)) >> shift;
+        return static_cast<std::uint8_t>(sign | (r - (static_cast<std::uint32_t>(127 - BIAS) << MANT)));
+    }
+    if (e < emin - MANT - 1) return static_cast<std::uint8_t>(sign);  // below half of the smallest subnormal
+    const std::uint32_t m = (mag & 0x007FFFFFu) | 0x00800000u;
+    const int shift = (23 - MANT) + (emin - e);  // <= 24: m >> shift is |f| in units of the smallest subnormal
+    const std::uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
+    return static_cast<std::uint8_t>(sign | (q + ((rem > halfway || (rem == halfway && (q & 1u))) ? 1u : 0u)));
+}
+template <int MANT, int BIAS>
+inline float widen_fp8(std::uint8_t b) {
+    const std::uint32_t sign = static_cast<std::uint32_t>(b & 0x80u) << 24;
+    const std::uint32_t e = (b & 0x7Fu) >> MANT, m = b & ((1u << MANT) - 1u);
+    if (e != 0) return bits_to_float(sign | ((e + 127u - BIAS) << 23) | (m << (23 - MANT)));
+    const float mag = static_cast<float>(m) * bits_to_float(static_cast<std::uint32_t>(127 + 1 - BIAS - MANT) << 23);
+    return sign ? -mag : mag;  // zero or subnormal: exact
+}
+}  // namespace detail
+
+struct float8_e4m3 {
+    std::uint8_t bits = 0;
+    float8_e4m3() = default;
+    explicit float8_e4m3(float f) : bits(detail::narrow_fp8<3, 7, 0x43F00000u, 0x7Fu>(f)) {}  // >= 480: NaN
+    static float8_e4m3 from_bits(std::uint8_t b) {
+        float8_e4m3 x;
+        x.bits = b;
+        return x;
+    }
+    explicit operator float() const {
+        if ((bits & 0x7Fu) == 0x7Fu) return detail::bits_to_float((static_cast<std::uint32_t>(bits & 0x80u) << 24) | 0x7FC00000u);
+        return detail::widen_fp8<3, 7>(bits);
+    }
+};
+
+struct float8_e5m2 {
+    std::uint8_t bits = 0;
+    float8_e5m2() = default;
+    explicit float8_e5m2(float f) : bits(detail::narrow_fp8<2, 15, 0x47800000u, 0x7Cu>(f)) {}  // >= 2^16: inf
+    static float8_e5m2 from_bits(std::uint8_t b) {
+        float8_e5m2 x;
+        x.bits = b;
+        return x;
+    }
+    explicit operator float() const {
+        const std::uint32_t sign = static_cast<std::uint32_t>(bits & 0x80u) << 24, m = bits & 0x03u;
+        if ((bits & 0x7Cu) == 0x7Cu) return detail::bits_to_float(sign | 0x7F800000u | (m << 21));  // inf, NaN
+        return detail::widen_fp8<2, 15>(bits);
+    }
+};
+
+inline float8_e4m3 operator+(float8_e4m3 a, float8_e4m3 b) { return float8_e4m3(static_cast<float>(a) + static_cast<float>(b)); }
+inline float8_e4m3 operator*(float8_e4m3 a, float8_e4m3 b) { return float8_e4m3(static_cast<float>(a) * static_cast<float>(b)); }
+inline bool operator<(float8_e4m3 a, float8_e4m3 b) { return static_cast<float>(a) < static_cast<float>(b); }
+inline bool operator==(float8_e4m3 a, float8_e4m3 b) { return static_cast<float>(a) == static_cast<float>(b); }
+inline float8_e5m2 operator+(float8_e5m2 a, float8_e5m2 b) { return float8_e5m2(static_cast<float>(a) + static_cast<float>(b)); }
+inline float8_e5m2 operator*(float8_e5m2 a, float8_e5m2 b) { return float8_e5m2(static_cast<float>(a) * static_cast<float>(b)); }
+inline bool operator<(float8_e5m2 a, float8_e5m2 b) { return static_cast<float>(a) < static_cast<float>(b); }
+inline bool operator==(float8_e5m2 a, float8_e5m2 b) { return static_cast<float>(a) == static_cast<float>(b); }
+static_assert(sizeof(float8_e4m3) == 1 && sizeof(float8_e5m2) == 1 && std::is_trivially_copyable_v<float8_e4m3> &&
+                  std::is_trivially_copyable_v<float8_e5m2>,
+              "8-bit float elements are their raw bits");
+
+// The float element types narrower than float: their values are held and scaled (the mean) in float.
+template <class A>
+inline constexpr bool narrow_float_v = std::is_same_v<A, half> || std::is_same_v<A, bfloat16> ||
+                                       std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>;
+
 // The C-ABI element type of a fundamental A (any integer type by width and signedness, so long long and
-// char map too) or of Dev::half / Dev::bfloat16, or -1: bool, long double and other types stay on the host.
+// char map too) or of Dev::half / Dev::bfloat16 / Dev::float8_e4m3 / Dev::float8_e5m2, or -1: bool, long double and
+// other types stay on the host.
 template <class A>
 constexpr int dtype_of() {
     if constexpr (std::is_same_v<A, float>) return FMI_F32;
     else if constexpr (std::is_same_v<A, double>) return FMI_F64;
     else if constexpr (std::is_same_v<A, half>) return FMI_F16;
     else if constexpr (std::is_same_v<A, bfloat16>) return FMI_BF16;
+    else if constexpr (std::is_same_v<A, float8_e4m3>) return FMI_F8E4M3;
+    else if constexpr (std::is_same_v<A, float8_e5m2>) return FMI_F8E5M2;
     else if constexpr (std::is_integral_v<A> && !std::is_same_v<A, bool>) {
         constexpr bool s = std::is_signed_v<A>;
         switch (sizeof(A)) {
@@ -153,7 +241,7 @@ inline void sync() { check(fmi_dev_sync(), "fmi_dev_sync"); }
 // A device-resident bucket of n elements of A (owning, move-only).
 template <class A>
 class Bucket {
-    static_assert(device_type<A>, "device buckets hold float, double, Dev::half, Dev::bfloat16 or 8/16/32/64-bit integers");
+    static_assert(device_type<A>, "device buckets hold float, double, Dev::half, Dev::bfloat16, Dev::float8_e4m3, Dev::float8_e5m2 or 8/16/32/64-bit integers");
 
 public:
     using value_type = A;
@@ -231,6 +319,16 @@ private:
     std::size_t n_ = 0;
     bool owns_ = true;
 };
+
+// dst = src converted element by element (fmi_dev_convert): between float, Dev::half, Dev::bfloat16, Dev::float8_e4m3 and
+// Dev::float8_e5m2, the value through float, one rounding in all. How float / bfloat16 data gets into an 8-bit float bucket.
+template <class D, class S>
+inline void convert(Bucket<D>& dst, const Bucket<S>& src, fmi_stream_t stream = nullptr) {
+    static_assert((std::is_same_v<D, float> || narrow_float_v<D>) && (std::is_same_v<S, float> || narrow_float_v<S>),
+                  "convert: float, Dev::half, Dev::bfloat16, Dev::float8_e4m3 or Dev::float8_e5m2 elements");
+    if (dst.size() != src.size()) throw std::runtime_error("Dev::convert: size mismatch");
+    check(fmi_dev_convert(dtype_of<D>(), dst.data(), dtype_of<S>(), src.data(), src.size(), stream), "fmi_dev_convert");
+}
 
 // Untyped device scratch used by the channel algorithms for temporaries of device-resident buckets.
 class Scratch {

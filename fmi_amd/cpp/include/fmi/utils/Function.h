@@ -25,6 +25,8 @@ template <class A>
 class Bucket;
 struct half;
 struct bfloat16;
+struct float8_e4m3;
+struct float8_e5m2;
 }  // namespace FMI::Dev
 
 namespace FMI::Utils {
@@ -81,7 +83,8 @@ A apply_op(Op op, A a, A b) {
 // Element types that have a mean, and the payload types T built on them.
 template <class A>
 inline constexpr bool mean_elem_v =
-    std::is_floating_point_v<A> || std::is_same_v<A, Dev::half> || std::is_same_v<A, Dev::bfloat16>;
+    std::is_floating_point_v<A> || std::is_same_v<A, Dev::half> || std::is_same_v<A, Dev::bfloat16> ||
+    std::is_same_v<A, Dev::float8_e4m3> || std::is_same_v<A, Dev::float8_e5m2>;
 template <class T>
 struct HasMean : std::bool_constant<std::is_floating_point_v<T>> {};
 template <class A>
@@ -128,7 +131,7 @@ public:
         : commutative(true), associative(true), f_(op == Op::avg ? nullptr : detail::HostBuiltin<T>::make(op)), op_(op) {
         if (op == Op::none) throw std::runtime_error("Function: Op::none is not a built-in op");
         if (op == Op::avg && !detail::HasMean<T>::value)
-            throw std::runtime_error("Function: Op::avg needs floating-point elements (float, double, Dev::half, Dev::bfloat16)");
+            throw std::runtime_error("Function: Op::avg needs floating-point elements (float, double, Dev::half, Dev::bfloat16, Dev::float8_e4m3, Dev::float8_e5m2)");
     }
 
     // Built-in op with the accumulation type of P-way collectives (above).

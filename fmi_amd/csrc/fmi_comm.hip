@@ -43,7 +43,7 @@
 namespace fmi::dev {
 namespace {
 
-constexpr size_t kShardAlign = 64;  // elements: shards stay 256-B aligned for the 16-B vector kernels
+constexpr size_t kShardAlign = 64;  // elements: shards stay 256-B aligned (64 B at 1-byte elements) for the 16-B vector kernels
 
 int hip_err(const char* what, hipError_t e) { return fail(FMI_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 
@@ -1696,7 +1696,7 @@ int allreduce_device(Comm* c, int op, int dtype, int kd, int alg, int path, cons
         for (int j = 0; j < N; ++j) parts[j] = staging + j * stride;
         if (per_rank) {
             FMI_COMM_RC(c->timing.begin(s));
-            if (N >= 2 && N <= sched::kMaxFusedPeers) {
+            if (N >= 2 && N <= sched::kMaxFusedPeers && fused_covers(op, dtype, FMI_ALG_ALLREDUCE, N)) {
                 PeerPtrs ptrs{};
                 for (int j = 0; j < N; ++j) {
                     ptrs.in[j] = parts[j];
@@ -1959,6 +1959,9 @@ static int comm_allreduce_impl(fmi_comm_t comm, int op, int dtype, int alg, int 
     int kd = 0;  // the shard step's dtype argument (check_common)
     FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
     FMI_COMM_RC(check_allreduce_args(alg, path));
+    if (path == FMI_PATH_RCCL && is_fp8_dtype(dtype))
+        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: the 8-bit float dtypes need path TREE or DIRECT (RCCL's reduction has its "
+                                         "own order and rounding)");
     if (path == FMI_PATH_RCCL && accumulates_f32(kd))
         return fail(FMI_ERR_UNSUPPORTED, "path RCCL: FMI_ACC_F32 needs path TREE or DIRECT (RCCL's reduction has its own order "
                                          "and rounding)");
@@ -1978,6 +1981,9 @@ static int comm_allreduce_host_impl(fmi_comm_t comm, int op, int dtype, int alg,
     int kd = 0;  // the shard step's dtype argument (check_common)
     FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
     FMI_COMM_RC(check_allreduce_args(alg, path));
+    if (path == FMI_PATH_RCCL && is_fp8_dtype(dtype))
+        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: the 8-bit float dtypes need path TREE or DIRECT (RCCL's reduction has its "
+                                         "own order and rounding)");
     if (path == FMI_PATH_RCCL && accumulates_f32(kd))
         return fail(FMI_ERR_UNSUPPORTED, "path RCCL: FMI_ACC_F32 needs path TREE or DIRECT (RCCL's reduction has its own order "
                                          "and rounding)");

@@ -295,8 +295,8 @@ int refuse_capture(hipStream_t s, const char* needs) {
 }
 
 int arena_acquire(size_t need, hipStream_t s) {
-    FMI_RC_TRY(refuse_capture(s, "the library's scratch arena (unaligned or 8/16-bit buckets, or a P-way program beyond "
-                                 "the fused kernels)"));
+    FMI_RC_TRY(refuse_capture(s, "the library's scratch arena (unaligned or 8/16-bit integer buckets, 8-bit float buckets "
+                                 "without FMI_ACC_F32, or a P-way program beyond the fused kernels)"));
     if (!g_state.arena_free) FMI_HIP_TRY(hipEventCreateWithFlags(&g_state.arena_free, hipEventDisableTiming));
     if (g_state.arena_bytes < need) {
         FMI_HIP_TRY(hipEventSynchronize(g_state.arena_free));  // previous users have drained
@@ -1472,14 +1472,14 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
             return reduce_tree_impl(avg ? FMI_OP_AVG : op, FMI_F32, alg, fo[0], fi, P, rank, n, stream);
         });
     }
-    if (avg && (P > sched::kMaxFusedPeers || !aligned)) {
+    if (avg && !acc && (P > sched::kMaxFusedPeers || !aligned || !fused_covers(op, dtype, alg, P))) {
         // beyond the fused mean kernels: the unchanged SUM program, then the scale kernel in place on its result
         if (int rc = reduce_tree_impl(FMI_OP_SUM, dtype, alg, out, ins, P, rank, n, stream)) return rc;
         return launch_mean_scale(dtype, out, n, P, s);
     }
     if (acc) dtype |= FMI_ACC_F32;  // launch_fused hands these to the acc32 units
     if (avg) op = FMI_OP_AVG;       // and these to the mean units: 2 <= P <= 16, aligned
-    if (P >= 2 && aligned && fused_covers(op, storage_dtype(dtype), alg, P)) {
+    if (P >= 2 && aligned && fused_covers_arg(op, dtype, alg, P)) {
         if (P > sched::max_fused_peers(alg)) return run_tree_blocked(op, dtype, alg, out, order.data(), P, rank, n, s);
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) ptrs.in[p] = order[p];
@@ -1523,7 +1523,7 @@ static int scan_peers_impl(int op, int dtype_arg, int alg, void* const* outs, co
         });
     }
     if (acc) dtype |= FMI_ACC_F32;  // launch_fused hands these to the acc32 units
-    if (P >= 2 && aligned && fused_covers(op, storage_dtype(dtype), alg, P)) {
+    if (P >= 2 && aligned && fused_covers_arg(op, dtype, alg, P)) {
         if (P > sched::max_fused_peers(alg)) return run_scan_blocked(op, dtype, alg, outs, ins, P, n, s);
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) {
@@ -1677,6 +1677,19 @@ int fmi_dev_mean_scale(int dtype, void* inout, size_t n, int P, fmi_stream_t str
         if (!inout) return fail(FMI_ERR_INVALID, "null buffer");
         if (int rc = require_device()) return rc;
         return launch_mean_scale(dtype, inout, n, P, resolve(stream));
+    });
+}
+
+int fmi_dev_convert(int dst_dtype, void* dst, int src_dtype, const void* src, size_t n, fmi_stream_t stream) {
+    return guarded("fmi_dev_convert", [&]() -> int {
+        for (const int d : {dst_dtype, src_dtype})
+            if (d != FMI_F32 && !is_half_dtype(d) && !is_fp8_dtype(d))
+                return fail(FMI_ERR_INVALID, "fmi_dev_convert: dtype " + std::to_string(d) + " is not one of FMI_F32, FMI_F16, "
+                                             "FMI_BF16, FMI_F8E4M3, FMI_F8E5M2 (FMI_ACC_F32 is not valid here)");
+        if (n == 0) return FMI_OK;
+        if (!dst || !src) return fail(FMI_ERR_INVALID, "null buffer");
+        if (int rc = require_device()) return rc;
+        return launch_convert(dst_dtype, dst, src_dtype, src, n, resolve(stream));
     });
 }
 

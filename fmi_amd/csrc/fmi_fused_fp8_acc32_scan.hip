@@ -1,0 +1,9 @@
+// FMI_ACC_F32 for the 8-bit float dtypes, P = 2..16 (fmi_fp8_impl.h): the fused kernels of
+// scan_no_order, every prefix its own f32 value narrowed once; sum and prod.
+#include "fmi_fp8_impl.h"
+
+namespace fmi::dev {
+int launch_fused_fp8_acc32_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
+    return launch_fused_fp8_acc32_family<sched::kScan>(op, dtype, P, ptrs, n, s);
+}
+}  // namespace fmi::dev

@@ -43,6 +43,11 @@ template <int ALG, bool RANK_AWARE, int LO = 2, int HI = sched::kMaxFusedPeers, 
 int launch_fused(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s) {
     static_assert(2 <= LO && LO <= HI && HI <= sched::max_fused_peers(ALG), "fused peer range");
     if constexpr (TIER == kTierCore) {
+        if (is_fp8_dtype(storage_dtype(dtype))) {
+            if (!accumulates_f32(dtype))
+                return fail(FMI_ERR_INVALID, "the 8-bit floats have fused kernels only with FMI_ACC_F32");
+            return launch_fused_fp8_acc32(ALG, op, storage_dtype(dtype), P, ptrs, n, s);
+        }
         if (op == FMI_OP_AVG) return launch_fused_avg(ALG, dtype, P, ptrs, n, s);
         if (accumulates_f32(dtype)) return launch_fused_acc32(ALG, op, dtype, P, ptrs, n, s);
         if (is_half_dtype(dtype)) return launch_fused_half(ALG, RANK_AWARE, op, dtype, P, ptrs, n, rank, s);

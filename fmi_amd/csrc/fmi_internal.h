@@ -47,21 +47,24 @@ inline bool is_core_dtype(int dtype) { return dtype >= FMI_F32 && dtype <= FMI_I
 // The 16-bit float dtypes: the pairwise family and every fused / one-pass family, each instantiated in the
 // fmi_fused_half_*.hip translation units.
 inline bool is_half_dtype(int dtype) { return dtype == FMI_F16 || dtype == FMI_BF16; }
+// The 8-bit float dtypes: the pairwise family, and with FMI_ACC_F32 the fused kernels of fmi_fused_fp8_acc32_*.hip.
+// Their plain P-way programs have no fused kernel (out of scope on purpose): they run as pairwise passes in order.
+inline bool is_fp8_dtype(int dtype) { return dtype == FMI_F8E4M3 || dtype == FMI_F8E5M2; }
 
 // The dtype ARGUMENT of a P-way call may carry FMI_ACC_F32 (include/fmi_dev.h): its storage dtype, which sizes,
 // alignment, order_sensitive, fused_covers and with_dtype take, and whether the program's values are kept in f32.
 inline int storage_dtype(int dtype_arg) { return dtype_arg & ~FMI_ACC_F32; }
 inline bool accumulates_f32(int dtype_arg) { return (dtype_arg & FMI_ACC_F32) != 0; }
-// What every entry point does with its dtype argument, once: the flag is valid on the two 16-bit float dtypes alone
+// What every entry point does with its dtype argument, once: the flag is valid on the 16-bit and 8-bit float dtypes alone
 // (FMI_ERR_INVALID naming the dtype otherwise), and it is dropped where it cannot change a bit: max / min are
 // selections, and a pairwise call (pway = false) or a single peer makes no second rounding. *canon: the storage
 // dtype, with the flag where the call accumulates in f32. An unknown storage dtype is left to the caller's own check.
 inline int canonical_dtype(int op, int dtype_arg, bool pway, int P, int* canon) {
     *canon = storage_dtype(dtype_arg);
     if (!accumulates_f32(dtype_arg)) return FMI_OK;
-    if (!is_half_dtype(*canon))
-        return fail(FMI_ERR_INVALID, "dtype " + std::to_string(dtype_arg) + ": FMI_ACC_F32 is valid only as FMI_F16 | FMI_ACC_F32 "
-                                     "or FMI_BF16 | FMI_ACC_F32");
+    if (!is_half_dtype(*canon) && !is_fp8_dtype(*canon))
+        return fail(FMI_ERR_INVALID, "dtype " + std::to_string(dtype_arg) + ": FMI_ACC_F32 is valid only as FMI_F16 | FMI_ACC_F32, "
+                                     "FMI_BF16 | FMI_ACC_F32, FMI_F8E4M3 | FMI_ACC_F32 or FMI_F8E5M2 | FMI_ACC_F32");
     if (pway && P != 1 && (op == FMI_OP_SUM || op == FMI_OP_PROD || op == FMI_OP_AVG)) *canon |= FMI_ACC_F32;
     return FMI_OK;
 }
@@ -83,6 +86,13 @@ inline bool fused_covers(int op, int dtype, int alg, int P) {
     (void)op, (void)alg, (void)P;
     return is_core_dtype(dtype) || is_half_dtype(dtype);
 }
+// The same question for a dtype ARGUMENT in canonical form: the 8-bit floats have fused kernels only with FMI_ACC_F32
+// (sum / prod / the mean, 2 <= P <= 16; the callers send P > 16 and unaligned buckets to the f32 fallback first).
+inline bool fused_covers_arg(int op, int dtype_arg, int alg, int P) {
+    const int st = storage_dtype(dtype_arg);
+    if (is_fp8_dtype(st)) return accumulates_f32(dtype_arg) && P <= sched::kMaxFusedPeers;
+    return fused_covers(op, st, alg, P);
+}
 
 // Dispatch tiers of with_dtype. The fused launch tables are built per tier: the core tier in the translation
 // units that always held them, the half tier in fmi_fused_half_*.hip (launch_fused routes there), so
@@ -92,6 +102,7 @@ inline constexpr int kTierAll = 1;   // every fmi_dtype_t
 inline constexpr int kTierHalf = 2;  // f16 bf16 alone
 inline constexpr int kTierF16 = 3;   // one of the two: the largest half-tier programs build one dtype per
 inline constexpr int kTierBF16 = 4;  // translation unit
+inline constexpr int kTierFp8 = 5;   // the two 8-bit floats alone (fmi_fused_fp8_acc32_*.hip, the conversions)
 
 // Invoke f.template operator()<T>() for a runtime dtype of the tier; returns FMI_ERR_INVALID if it is not in it.
 template <int TIER, class F>
@@ -109,6 +120,10 @@ int with_dtype(int dtype, F&& f) {
         if (dtype == FMI_F16) return f.template operator()<_Float16>();
     if constexpr (TIER == kTierAll || TIER == kTierHalf || TIER == kTierBF16)
         if (dtype == FMI_BF16) return f.template operator()<__bf16>();
+    if constexpr (TIER == kTierAll || TIER == kTierFp8) {
+        if (dtype == FMI_F8E4M3) return f.template operator()<f8e4m3>();
+        if (dtype == FMI_F8E5M2) return f.template operator()<f8e5m2>();
+    }
     if constexpr (TIER == kTierAll) {
         switch (dtype) {
             case FMI_U32: return f.template operator()<uint32_t>();
@@ -142,13 +157,13 @@ inline size_t dtype_size(int dtype) {
     switch (dtype) {
         case FMI_F32: case FMI_I32: case FMI_U32: return 4;
         case FMI_F64: case FMI_I64: case FMI_U64: return 8;
-        case FMI_I8: case FMI_U8: return 1;
+        case FMI_I8: case FMI_U8: case FMI_F8E4M3: case FMI_F8E5M2: return 1;
         case FMI_I16: case FMI_U16: case FMI_F16: case FMI_BF16: return 2;
         default: return 0;
     }
 }
 
-inline bool is_float(int dtype) { return dtype == FMI_F32 || dtype == FMI_F64 || is_half_dtype(dtype); }
+inline bool is_float(int dtype) { return dtype == FMI_F32 || dtype == FMI_F64 || is_half_dtype(dtype) || is_fp8_dtype(dtype); }
 
 // Fused single-pass launches (P in [2, kMaxFusedPeers], all pointers 16-B aligned). One function per
 // algorithm family, each defined in its own translation unit so the ~1.2k instantiations build in
@@ -191,6 +206,16 @@ int launch_fused_acc32_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs
 int launch_fused_acc32_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_acc32_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_acc32_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+// The same for the 8-bit floats (dtype = FMI_F8E4M3 / FMI_F8E5M2 | FMI_ACC_F32; op sum, prod or, at the three reduce
+// algorithms, FMI_OP_AVG; 2 <= P <= 16): launch_fused hands these to launch_fused_fp8_acc32 (fmi_fused_fp8_acc32.hip),
+// which picks the family's translation unit (fmi_fused_fp8_acc32_*.hip); the units take the storage dtype.
+int launch_fused_fp8_acc32(int alg, int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_fp8_acc32_allreduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_fp8_acc32_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_fp8_acc32_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_fp8_acc32_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_fp8_acc32_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+int launch_fused_fp8_acc32_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // FMI_OP_AVG at 2 <= P <= 16 (alg: one of the three reduce algorithms; dtype: a float storage dtype, with FMI_ACC_F32
 // where the values are f32): launch_fused hands these to launch_fused_avg (fmi_fused_avg.hip), which picks the
 // algorithm's translation unit (fmi_fused_avg_*.hip).
@@ -199,12 +224,15 @@ int launch_fused_avg_allreduce(int dtype, int P, const PeerPtrs& ptrs, size_t n,
 int launch_fused_avg_reduce(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 int launch_fused_avg_reduce_ltr(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // The mean's scale step alone (fmi_scale.hip), in place, any alignment: inout[i] = store(fl_V(value(inout[i]) * fl_V(1 / P))).
-// dtype: one of the four float dtypes.
+// dtype: one of the six float dtypes.
 int launch_mean_scale(int dtype, void* inout, size_t n, int P, hipStream_t s);
 // The fallback's streaming conversions (fmi_acc32_convert.hip), any alignment: dst[i] = (float)src[i] (exact) and
-// dst[i] = the storage type's rounding of src[i]. dtype: FMI_F16 or FMI_BF16.
+// dst[i] = the storage type's rounding of src[i]. dtype: FMI_F16, FMI_BF16, FMI_F8E4M3 or FMI_F8E5M2.
 int launch_widen_f32(int dtype, float* dst, const void* src, size_t n, hipStream_t s);
 int launch_narrow_f32(int dtype, void* dst, const float* src, size_t n, hipStream_t s);
+// fmi_dev_convert: dst[i] = narrow_dst(widen_src(src[i])) between any two of f32 / f16 / bf16 / E4M3 / E5M2 (equal
+// dtypes: the bits copied), one launch, any alignment, dst == src allowed at equal element size.
+int launch_convert(int dst_dtype, void* dst, int src_dtype, const void* src, size_t n, hipStream_t s);
 int launch_fused_half_allreduce(int op, int dtype, bool rank_aware, int P, const PeerPtrs& ptrs, size_t n, int rank,
                                 hipStream_t s);
 int launch_fused_half_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);

@@ -9,7 +9,7 @@
 //   scan_kernel               outs[k]= program_k(x0..x{P-1})   one pass: P reads + P writes
 //   synth_kernel              counter-based synthetic buckets (splitmix64), identical to the host
 //
-// Every access is a 16-B global_load_dwordx4 / global_store_dwordx4 (4 f32/i32, 2 f64/i64 or 8 f16/bf16 lanes);
+// Every access is a 16-B global_load_dwordx4 / global_store_dwordx4 (4 f32/i32, 2 f64/i64, 8 f16/bf16 or 16 8-bit lanes);
 // the < 16-B remainder of a bucket is handled by the first threads of block 0 with scalar accesses,
 // so a launch never touches a byte outside [0, n).
 #pragma once
@@ -49,10 +49,86 @@ struct Wrap<__bf16> {
 };
 template <class T>
 inline constexpr bool is_half_float_v = std::is_same_v<T, _Float16> || std::is_same_v<T, __bf16>;
+
+// The 8-bit float elements (FMI_F8E4M3, FMI_F8E5M2: the OCP formats, include/fmi_dev.h): one byte each, as wrapper
+// types of their own so that uint8_t keeps meaning FMI_U8. The rule of the 16-bit floats holds: one combine widens both
+// operands to f32 (exact), applies the op in f32 and narrows, after EVERY combine of a plain P-way program; max / min
+// compare the widened values and keep one operand's byte. Narrowing is round-to-nearest-even with subnormals kept and
+// does NOT saturate: a rounded magnitude beyond the largest finite value (or +-inf) gives +-inf (E5M2) or NaN (E4M3).
+struct f8e4m3 {
+    uint8_t b;
+};
+struct f8e5m2 {
+    uint8_t b;
+};
+template <class T>
+inline constexpr bool is_fp8_v = std::is_same_v<T, f8e4m3> || std::is_same_v<T, f8e5m2>;
+// The float elements narrower than their f32 value type
+template <class T>
+inline constexpr bool is_narrow_float_v = is_half_float_v<T> || is_fp8_v<T>;
+
+// f32 -> fp8 in integer code, by the definition: what the synthetic buckets narrow with, on the host and on the device
+// alike (their values are exact in the format). M mantissa bits, B the bias.
+template <class T>
+__host__ __device__ __forceinline__ uint8_t fp8_narrow_sw(float f) {
+    constexpr bool k5 = std::is_same_v<T, f8e5m2>;
+    constexpr int M = k5 ? 2 : 3, B = k5 ? 15 : 7, emin = 1 - B;
+    // the first magnitude that no longer rounds to a finite value or, by the carry out of the mantissa, to the
+    // format's own inf / NaN pattern: 2^16 (E5M2: [61440, 2^16) carries into 0x7C), 480 (E4M3: (464, 480) carries into 0x7F)
+    constexpr uint32_t over = k5 ? 0x47800000u : 0x43F00000u;
+    const uint32_t u = __builtin_bit_cast(uint32_t, f);
+    const uint32_t s = (u >> 24) & 0x80u, a = u & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return static_cast<uint8_t>(s | 0x7Fu);
+    if (a >= over) return static_cast<uint8_t>(s | (k5 ? 0x7Cu : 0x7Fu));
+    const int e = static_cast<int>(a >> 23) - 127;
+    if (e >= emin) {
+        constexpr int shift = 23 - M;
+        const uint32_t r = (a + ((1u << (shift - 1)) - 1u) + ((a >> shift) & 1u)) >> shift;
+        return static_cast<uint8_t>(s | (r - (static_cast<uint32_t>(127 - B) << M)));
+    }
+    if (e < emin - M - 1) return static_cast<uint8_t>(s);  // below half the smallest subnormal
+    const uint32_t mant = (a & 0x7FFFFFu) | 0x800000u;
+    const int shift = (23 - M) + (emin - e);  // <= 24
+    uint32_t r = mant >> shift;
+    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    if (rem > half || (rem == half && (r & 1u))) ++r;
+    return static_cast<uint8_t>(s | r);
+}
+
+// The hardware conversions (v_cvt_pk_f32_fp8 / _bf8, v_cvt_pk_fp8_f32 / _bf8_f32: the OCP encodings on gfx950, no
+// clamp): they equal the definition on every input compared.
+
+// the two elements in the low (HI = false) or high half of a word, widened
+template <class T, bool HI>
+__device__ __forceinline__ float __attribute__((ext_vector_type(2))) fp8_widen2(uint32_t w) {
+    if constexpr (std::is_same_v<T, f8e4m3>)
+        return __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(w), HI);
+    else
+        return __builtin_amdgcn_cvt_pk_f32_bf8(static_cast<int>(w), HI);
+}
+// `old` with its low / high half replaced by (narrow(x), narrow(y))
+template <class T, bool HI>
+__device__ __forceinline__ uint32_t fp8_narrow2(float x, float y, uint32_t old) {
+    if constexpr (std::is_same_v<T, f8e4m3>) {
+        return static_cast<uint32_t>(__builtin_amdgcn_cvt_pk_fp8_f32(x, y, static_cast<int>(old), HI));
+    } else {
+        return static_cast<uint32_t>(__builtin_amdgcn_cvt_pk_bf8_f32(x, y, static_cast<int>(old), HI));
+    }
+}
+template <class T>
+__device__ __forceinline__ float fp8_widen(T x) {
+    return fp8_widen2<T, false>(x.b).x;
+}
+template <class T>
+__device__ __forceinline__ T fp8_narrow(float f) {
+    return T{static_cast<uint8_t>(fp8_narrow2<T, false>(f, f, 0u) & 0xFFu)};
+}
+__device__ __forceinline__ bool operator<(f8e4m3 a, f8e4m3 b) { return fp8_widen(a) < fp8_widen(b); }
+__device__ __forceinline__ bool operator<(f8e5m2 a, f8e5m2 b) { return fp8_widen(a) < fp8_widen(b); }
 // "Is a float element" (operand order can change the bits of max / min): the library's own answer, not
 // libstdc++'s, which differs between versions for the two 16-bit types.
 template <class T>
-inline constexpr bool is_float_elem_v = std::is_same_v<T, float> || std::is_same_v<T, double> || is_half_float_v<T>;
+inline constexpr bool is_float_elem_v = std::is_same_v<T, float> || std::is_same_v<T, double> || is_narrow_float_v<T>;
 template <>
 struct Wrap<int32_t> {
     using type = uint32_t;
@@ -83,15 +159,23 @@ struct Wrap<uint16_t> {
 struct OpSum {
     template <class T>
     __device__ __forceinline__ static T apply(T a, T b) {
-        using U = typename Wrap<T>::type;
-        return static_cast<T>(static_cast<U>(a) + static_cast<U>(b));
+        if constexpr (is_fp8_v<T>) {
+            return fp8_narrow<T>(fp8_widen(a) + fp8_widen(b));
+        } else {
+            using U = typename Wrap<T>::type;
+            return static_cast<T>(static_cast<U>(a) + static_cast<U>(b));
+        }
     }
 };
 struct OpProd {
     template <class T>
     __device__ __forceinline__ static T apply(T a, T b) {
-        using U = typename Wrap<T>::type;
-        return static_cast<T>(static_cast<U>(a) * static_cast<U>(b));
+        if constexpr (is_fp8_v<T>) {
+            return fp8_narrow<T>(fp8_widen(a) * fp8_widen(b));
+        } else {
+            using U = typename Wrap<T>::type;
+            return static_cast<T>(static_cast<U>(a) * static_cast<U>(b));
+        }
     }
 };
 struct OpMax {
@@ -134,7 +218,8 @@ struct LaneStorage {
 };
 template <class T, int W>
 struct LaneStorage<T, W, true> {
-    T __attribute__((ext_vector_type(W))) v;
+    // the 8-bit floats as their bytes: a lane group of them is only ever read as 32-bit words
+    std::conditional_t<is_fp8_v<T>, uint8_t, T> __attribute__((ext_vector_type(W))) v;
 };
 
 template <class T, int W>
@@ -253,9 +338,46 @@ __device__ __forceinline__ uint32_t combine_halves(uint32_t a, uint32_t b) {
     }
 }
 
+// 8-bit float lanes, four per 32-bit word, the same bits as Op::apply<T> per element. sum / prod: both halves of each
+// word widened by the packed conversions, v_pk_add_f32 / v_pk_mul_f32, and the four results narrowed two at a time
+// into the low and the high half of the result word. max / min: compare the widened values per byte and keep the
+// operand's own byte (never re-narrowed).
+template <class Op, class T>
+__device__ __forceinline__ uint32_t combine_fp8(uint32_t a, uint32_t b) {
+    const f32x2 al = fp8_widen2<T, false>(a), ah = fp8_widen2<T, true>(a);
+    const f32x2 bl = fp8_widen2<T, false>(b), bh = fp8_widen2<T, true>(b);
+    if constexpr (std::is_same_v<Op, OpMax> || std::is_same_v<Op, OpMin>) {
+        constexpr bool kMax = std::is_same_v<Op, OpMax>;  // mask: take b's byte
+        const uint32_t m = ((kMax ? (al.x < bl.x) : (bl.x < al.x)) ? 0x000000FFu : 0u) |
+                           ((kMax ? (al.y < bl.y) : (bl.y < al.y)) ? 0x0000FF00u : 0u) |
+                           ((kMax ? (ah.x < bh.x) : (bh.x < ah.x)) ? 0x00FF0000u : 0u) |
+                           ((kMax ? (ah.y < bh.y) : (bh.y < ah.y)) ? 0xFF000000u : 0u);
+        return (b & m) | (a & ~m);
+    } else {
+        f32x2 rl, rh;
+        if constexpr (std::is_same_v<Op, OpSum>) {
+            rl = al + bl;
+            rh = ah + bh;
+        } else {
+            rl = al * bl;
+            rh = ah * bh;
+        }
+        return fp8_narrow2<T, true>(rh.x, rh.y, fp8_narrow2<T, false>(rl.x, rl.y, 0u));
+    }
+}
+
 template <class Op, class T, int W, bool REWIDEN = false>
 __device__ __forceinline__ Lanes<T, W> combine(const Lanes<T, W>& a, const Lanes<T, W>& b) {
-    if constexpr (is_half_float_v<T> && W % 2 == 0) {
+    if constexpr (is_fp8_v<T> && W % 4 == 0) {
+        struct Words {
+            uint32_t w[W / 4];
+        };
+        const Words x = __builtin_bit_cast(Words, a), y = __builtin_bit_cast(Words, b);
+        Words r;
+#pragma unroll
+        for (int k = 0; k < W / 4; ++k) r.w[k] = combine_fp8<Op, T>(x.w[k], y.w[k]);
+        return __builtin_bit_cast(Lanes<T, W>, r);
+    } else if constexpr (is_half_float_v<T> && W % 2 == 0) {
         struct Words {
             uint32_t w[W / 2];
         };
@@ -307,9 +429,25 @@ __device__ __forceinline__ Lanes<V, W> to_value(const Lanes<T, W>& x) {
     if constexpr (std::is_same_v<V, T>) {
         return x;
     } else {
-        static_assert(std::is_same_v<V, float> && is_half_float_v<T>, "f32 values of 16-bit float storage");
+        static_assert(std::is_same_v<V, float> && is_narrow_float_v<T>, "f32 values of 8- or 16-bit float storage");
         Lanes<V, W> r;
-        if constexpr (std::is_same_v<T, __bf16> && W % 2 == 0) {
+        if constexpr (is_fp8_v<T> && W % 4 == 0) {
+            struct Words {
+                uint32_t w[W / 4];
+            };
+            const Words p = __builtin_bit_cast(Words, x);
+#pragma unroll
+            for (int k = 0; k < W / 4; ++k) {
+                const f32x2 lo = fp8_widen2<T, false>(p.w[k]), hi = fp8_widen2<T, true>(p.w[k]);
+                r.v[4 * k] = lo.x;
+                r.v[4 * k + 1] = lo.y;
+                r.v[4 * k + 2] = hi.x;
+                r.v[4 * k + 3] = hi.y;
+            }
+        } else if constexpr (is_fp8_v<T>) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) r.v[k] = fp8_widen(x.v[k]);
+        } else if constexpr (std::is_same_v<T, __bf16> && W % 2 == 0) {
             struct Words {
                 uint32_t w[W / 2];
             };
@@ -332,9 +470,20 @@ __device__ __forceinline__ Lanes<T, W> to_storage(const Lanes<V, W>& x) {
     if constexpr (std::is_same_v<V, T>) {
         return x;
     } else {
-        static_assert(std::is_same_v<V, float> && is_half_float_v<T>, "f32 values of 16-bit float storage");
+        static_assert(std::is_same_v<V, float> && is_narrow_float_v<T>, "f32 values of 8- or 16-bit float storage");
         Lanes<T, W> r;
-        if constexpr (std::is_same_v<T, __bf16> && W % 2 == 0) {
+        if constexpr (is_fp8_v<T> && W % 4 == 0) {
+            struct Words {
+                uint32_t w[W / 4];
+            } p;
+#pragma unroll
+            for (int k = 0; k < W / 4; ++k)
+                p.w[k] = fp8_narrow2<T, true>(x.v[4 * k + 2], x.v[4 * k + 3], fp8_narrow2<T, false>(x.v[4 * k], x.v[4 * k + 1], 0u));
+            r = __builtin_bit_cast(Lanes<T, W>, p);
+        } else if constexpr (is_fp8_v<T>) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) r.v[k] = fp8_narrow<T>(x.v[k]);
+        } else if constexpr (std::is_same_v<T, __bf16> && W % 2 == 0) {
             struct Words {
                 uint32_t w[W / 2];
             } p;
@@ -367,7 +516,7 @@ __device__ __forceinline__ Lanes<T, W> to_storage(const Lanes<V, W>& x) {
 // otherwise fuses multiply and narrowing into v_fma_mixlo_f16 x, y, +0 (to_storage above), and -0 * r comes out as +0.
 template <class T, int P, class V, int W>
 __device__ __forceinline__ Lanes<T, W> finish_avg(const Lanes<V, W>& x) {
-    if constexpr (is_half_float_v<T>) {
+    if constexpr (is_narrow_float_v<T>) {
         constexpr float r = 1.0f / static_cast<float>(P);
         Lanes<float, W> f = to_value<float>(x);
 #pragma unroll
@@ -783,6 +932,12 @@ __host__ __device__ __forceinline__ T synth_value(uint64_t h) {
     } else if constexpr (std::is_same_v<T, __bf16>) {
         // multiples of 2^-7 in [-1, 1): exact in f32 and in bf16 (at most 8 significant bits)
         return static_cast<__bf16>(static_cast<float>(h >> 56) * 0x1p-8f * 2.0f - 1.0f);
+    } else if constexpr (std::is_same_v<T, f8e4m3>) {
+        // multiples of 2^-3 in [-1, 1): exact in f32 and in E4M3 (at most 4 significant bits)
+        return f8e4m3{fp8_narrow_sw<f8e4m3>(static_cast<float>(h >> 60) * 0x1p-4f * 2.0f - 1.0f)};
+    } else if constexpr (std::is_same_v<T, f8e5m2>) {
+        // multiples of 2^-2 in [-1, 1): exact in f32 and in E5M2 (at most 3 significant bits)
+        return f8e5m2{fp8_narrow_sw<f8e5m2>(static_cast<float>(h >> 61) * 0x1p-3f * 2.0f - 1.0f)};
     } else {
         // integers: the top 8·sizeof(T) bits of h (i32 = h >> 32, i64 = h, as before)
         using U = std::make_unsigned_t<T>;

@@ -1,7 +1,7 @@
 // The scale kernel of FMI_OP_AVG (fmi_dev_mean_scale, and every mean call beyond the fused kernels: P > 16 or
 // unaligned buckets run the unchanged SUM program and then this on its result): in place,
 //   inout[i] = store(fl_V(value(inout[i]) * r)),  r = fl_V(1 / P) computed on the host,
-// V = f32 for f32 / f16 / bf16 and f64 for f64: one IEEE multiply and, for the 16-bit floats, the narrowing
+// V = f32 for f32 / f16 / bf16 / E4M3 / E5M2 and f64 for f64: one IEEE multiply and, for the 8- and 16-bit floats, the narrowing
 // Op::apply ends with (to_storage), from an opaque register so that multiply and narrowing are not fused into
 // v_fma_mixlo_f16 x, y, +0 (-0 would come out as +0). One 16-B nontemporal load and store per thread and step on an
 // aligned bucket, its < 16-B remainder by the first threads of workgroup 0; one element per thread on an unaligned
@@ -19,7 +19,7 @@ using ScaleValue = std::conditional_t<std::is_same_v<T, double>, double, float>;
 
 template <class T, int W>
 __device__ __forceinline__ Lanes<T, W> scale_lanes(const Lanes<T, W>& x, ScaleValue<T> r) {
-    if constexpr (is_half_float_v<T>) {
+    if constexpr (is_narrow_float_v<T>) {
         Lanes<float, W> f = to_value<float>(x);
 #pragma unroll
         for (int k = 0; k < W; ++k) {
@@ -79,6 +79,8 @@ int launch_mean_scale(int dtype, void* inout, size_t n, int P, hipStream_t s) {
         case FMI_F64: return launch<double>(inout, n, P, s);
         case FMI_F16: return launch<_Float16>(inout, n, P, s);
         case FMI_BF16: return launch<__bf16>(inout, n, P, s);
+        case FMI_F8E4M3: return launch<f8e4m3>(inout, n, P, s);
+        case FMI_F8E5M2: return launch<f8e5m2>(inout, n, P, s);
         default: return fail(FMI_ERR_INVALID, "FMI_OP_AVG: dtype " + std::to_string(dtype) + " is not a float dtype");
     }
 }

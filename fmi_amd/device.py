@@ -32,7 +32,9 @@ class DType(enum.IntEnum):
     """fmi_dtype_t. F32 / F64 / I32 / I64 run every kernel, and so do F16 (IEEE binary16) and BF16 (the upper half
     of binary32): the pairwise kernels and every fused / one-pass P-way form, at all five algorithms and any number
     of peers; every combine widens to f32 and rounds back to the storage type (include/fmi_dev.h). The other integer
-    widths run the pairwise kernel, and their P-way programs run as pairwise passes (as unaligned buckets do)."""
+    widths run the pairwise kernel, and their P-way programs run as pairwise passes (as unaligned buckets do).
+    F8E4M3 / F8E5M2 are the two OCP 8-bit floats (e4m3fn, e5m2; non-saturating narrowing): the pairwise kernels, fused
+    P-way kernels with accumulate_f32 up to 16 peers, and pairwise passes for the plain P-way programs."""
     F32 = 0
     F64 = 1
     I32 = 2
@@ -45,9 +47,11 @@ class DType(enum.IntEnum):
     U16 = 9
     F16 = 10
     BF16 = 11
+    F8E4M3 = 12
+    F8E5M2 = 13
 
 
-# fmi_dev.h's FMI_ACC_F32: ORed into the dtype argument of a P-way call on F16 / BF16 buckets, the program's values
+# fmi_dev.h's FMI_ACC_F32: ORed into the dtype argument of a P-way call on F16 / BF16 / F8E4M3 / F8E5M2 buckets, the program's values
 # are kept in f32 and every stored output is rounded to the storage type once (`accumulate_f32=True` below).
 ACC_F32 = 0x100
 
@@ -56,8 +60,8 @@ def acc_dtype(dtype: "DType", accumulate_f32: bool) -> int:
     """The dtype argument of a P-way call: the storage dtype, with ACC_F32 when `accumulate_f32`."""
     if not accumulate_f32:
         return int(dtype)
-    if dtype not in (DType.F16, DType.BF16):
-        raise ValueError(f"accumulate_f32 needs F16 or BF16 buckets, got {DType(dtype).name}")
+    if dtype not in (DType.F16, DType.BF16, DType.F8E4M3, DType.F8E5M2):
+        raise ValueError(f"accumulate_f32 needs F16 or BF16 (or F8E4M3 / F8E5M2) buckets, got {DType(dtype).name}")
     return int(dtype) | ACC_F32
 
 
@@ -92,8 +96,9 @@ class Tune(enum.IntEnum):
 NP_DTYPE = {DType.F32: np.float32, DType.F64: np.float64, DType.I32: np.int32, DType.I64: np.int64,
             DType.U32: np.uint32, DType.U64: np.uint64, DType.I8: np.int8, DType.U8: np.uint8, DType.I16: np.int16,
             DType.U16: np.uint16, DType.F16: np.float16}
-# numpy has no bfloat16: a BF16 bucket moves its elements' raw bits as np.uint16
-_HOST_DTYPE = {**NP_DTYPE, DType.BF16: np.uint16}
+# numpy has no bfloat16 and no 8-bit floats: a BF16 bucket moves its elements' raw bits as np.uint16, an F8E4M3 /
+# F8E5M2 bucket as np.uint8 (np.uint8 alone keeps meaning U8)
+_HOST_DTYPE = {**NP_DTYPE, DType.BF16: np.uint16, DType.F8E4M3: np.uint8, DType.F8E5M2: np.uint8}
 
 
 def dtype_of(arr_or_dtype) -> DType:
@@ -374,8 +379,8 @@ def _ptr_array(buckets: Sequence[Bucket]):
 
 def reduce_tree(op: Op, alg: Alg, out: Bucket, ins: Sequence[Bucket], rank: int = 0, stream=None,
                 accumulate_f32: bool = False) -> None:
-    """P-way reduction with a reference collective's bracketing (see include/fmi_dev.h). accumulate_f32 (F16 / BF16
-    buckets): the same program on f32 values, the result rounded to the storage type once."""
+    """P-way reduction with a reference collective's bracketing (see include/fmi_dev.h). accumulate_f32 (F16 / BF16 /
+    F8E4M3 / F8E5M2 buckets): the same program on f32 values, the result rounded to the storage type once."""
     dtype = acc_dtype(out.dtype, accumulate_f32)
     _check_peers(out, ins)
     _lib.call("fmi_dev_reduce_tree", int(op), dtype, int(alg), out.ptr, _ptr_array(ins), len(ins), rank,
@@ -391,10 +396,20 @@ def mean_scale(inout: Bucket, P: int, n: Optional[int] = None, stream=None) -> N
     _lib.call("fmi_dev_mean_scale", int(inout.dtype), inout.ptr, n, int(P), _sptr(stream))
 
 
+def convert(dst: Bucket, src: Bucket, n: Optional[int] = None, stream=None) -> None:
+    """dst = src converted to dst's dtype (fmi_dev_convert), between F32, F16, BF16, F8E4M3 and F8E5M2: the value goes
+    through f32, one rounding in all (to the 8-bit floats non-saturating). How f32 / bf16 data gets into an 8-bit float
+    bucket. dst may be src at equal element size."""
+    n = dst.n if n is None else n
+    if dst.n < n or src.n < n:
+        raise ValueError("convert: both buckets must hold n elements")
+    _lib.call("fmi_dev_convert", int(dst.dtype), dst.ptr, int(src.dtype), src.ptr, n, _sptr(stream))
+
+
 def scan_peers(op: Op, alg: Alg, outs: Sequence[Bucket], ins: Sequence[Bucket], stream=None,
                accumulate_f32: bool = False) -> None:
     """Peer-axis inclusive scan with the bracketing of reference scan_no_order / scan_ltr. accumulate_f32 (F16 /
-    BF16 buckets): the same program on f32 values, every prefix rounded to the storage type once."""
+    BF16 / F8E4M3 / F8E5M2 buckets): the same program on f32 values, every prefix rounded to the storage type once."""
     if len(outs) != len(ins):
         raise ValueError("scan_peers: one output bucket per peer")
     dtype = acc_dtype(outs[0].dtype, accumulate_f32)
@@ -404,13 +419,18 @@ def scan_peers(op: Op, alg: Alg, outs: Sequence[Bucket], ins: Sequence[Bucket], 
               len(ins), outs[0].n, _sptr(stream))
 
 
-def host_reduce_pair(op: Op, inout: np.ndarray, src: np.ndarray) -> None:
-    """inout = op(inout, src) for host arrays, streamed through the device (H2D, kernel, D2H)."""
+def host_reduce_pair(op: Op, inout: np.ndarray, src: np.ndarray, dtype: Optional[DType] = None) -> None:
+    """inout = op(inout, src) for host arrays, streamed through the device (H2D, kernel, D2H). `dtype`: the element
+    type where the arrays carry raw bits (DType.BF16 over np.uint16, DType.F8E4M3 / F8E5M2 over np.uint8); None = the
+    arrays' own."""
     if inout.dtype != src.dtype or inout.size != src.size:
         raise ValueError("host_reduce_pair: arrays must share dtype and size")
     if not (inout.flags.c_contiguous and src.flags.c_contiguous):
         raise ValueError("host_reduce_pair: arrays must be contiguous")
-    _lib.call("fmi_host_reduce_pair", int(op), int(dtype_of(inout)), inout.ctypes.data, src.ctypes.data, inout.size)
+    dt = dtype_of(inout) if dtype is None else DType(dtype)
+    if np.dtype(_HOST_DTYPE[dt]).itemsize != inout.dtype.itemsize:
+        raise ValueError("host_reduce_pair: the arrays' element size is not the dtype's")
+    _lib.call("fmi_host_reduce_pair", int(op), int(dt), inout.ctypes.data, src.ctypes.data, inout.size)
 
 
 class PinnedArray:

@@ -60,7 +60,8 @@ typedef enum { FMI_OP_SUM = 0, FMI_OP_PROD = 1, FMI_OP_MAX = 2, FMI_OP_MIN = 3, 
 /* FMI_OP_AVG = 5: the mean over the peers. Id 4 stays unassigned in the C-ABI: the reference's Python enum gives 4
  * to CUSTOM. Additive: fmi_abi_version() stays 1. A call with FMI_OP_AVG over P peers stores
  *     out = store( fl_V( S x r_P ) )
- *   V    the value type: f32 for FMI_F32, FMI_F16 and FMI_BF16 (with or without FMI_ACC_F32); f64 for FMI_F64.
+ *   V    the value type: f32 for FMI_F32, FMI_F16, FMI_BF16, FMI_F8E4M3 and FMI_F8E5M2 (with or without FMI_ACC_F32);
+ *        f64 for FMI_F64.
  *   S    what the same call with FMI_OP_SUM and the same `alg` holds in V just before its store. Plain dtypes: S is
  *        the SUM result itself (for f16 / bf16 already rounded to storage after every combine; it is widened).
  *        With FMI_ACC_F32: S is the f32 program value, not yet narrowed, so the result is
@@ -106,20 +107,47 @@ typedef enum { FMI_OP_SUM = 0, FMI_OP_PROD = 1, FMI_OP_MAX = 2, FMI_OP_MIN = 3, 
  * and any P on 16-B aligned buckets (fused up to 31 peers, the one-pass chains, blocked trees, pre-fold allreduces
  * and blocked scans beyond, superblocks past 128), and with them the shard kernels of fmi_comm_allreduce / reduce /
  * scan and fmi_comm_reduce_sendbuf's partials at any number of ranks. Only unaligned buckets run as pairwise passes
- * in the same order (the 16-bit integers' path), bit for bit the same values. Additive: fmi_abi_version() stays 1. */
+ * in the same order (the 16-bit integers' path), bit for bit the same values. Additive: fmi_abi_version() stays 1.
+ *
+ * FMI_F8E4M3 and FMI_F8E5M2: the two OCP 8-bit floats (gfx950's own encodings, not MI300's fnuz ones). Buckets are
+ * arrays of bytes.
+ *   FMI_F8E4M3 = 12  OCP E4M3 (e4m3fn): bias 7, no infinities, NaN = S.1111.111 only, largest finite 448, subnormals
+ *                    down to 2^-9.
+ *   FMI_F8E5M2 = 13  OCP E5M2: bias 15, IEEE-style infinities and NaNs, largest finite 57344, subnormals down to 2^-16.
+ * Widen (fp8 -> f32) is exact for every one of the 256 patterns; a NaN widens to some NaN.
+ * Narrow (f32 -> fp8) rounds to nearest even at the format's precision, keeps subnormals and the zero's sign, and does
+ * NOT saturate: if the rounded magnitude exceeds the largest finite value, or the input is +-inf, E5M2 gives +-inf and
+ * E4M3 gives NaN; NaN stays NaN (E4M3: 464 -> 0x7E, the tie to even, 448; 465 -> 0x7F, NaN. E5M2: 61440 -> 0x7C, the
+ * tie to even, inf; 61439.9 -> 0x7B). This is what tensor.to(torch.float8_e4m3fn / float8_e5m2) computes on the CPU.
+ * Deliberate: a reduction that overflows its storage type should show it, not return 448. A NaN result is some NaN.
+ * One combine follows the f16 / bf16 rule: widen both operands, apply the op in f32 (round-to-nearest-even, subnormals
+ * kept, no contraction), narrow; after EVERY combine of a plain P-way program, in the program's own order. The f32
+ * intermediate is part of the definition (an E5M2 sum is not always exact in f32; an E4M3 sum is). MAX / MIN are
+ * selections on the widened compare: the kept operand's byte comes out unchanged, so +-0 and NaN depend on the rank as
+ * for f32.
+ * Every pairwise entry point serves them (fmi_dev_reduce_pair, _batch, fmi_dev_combine, fmi_host_reduce_pair,
+ * fmi_dev_mean_scale, fmi_dev_fill_synthetic*). With FMI_ACC_F32 (below), SUM / PROD / FMI_OP_AVG at 2 <= P <= 16 on
+ * 16-B aligned buckets run ONE fused kernel at all five algorithms and for reduce partials: the form a gradient bucket
+ * wants. PLAIN 8-bit float P-way programs (no flag) have no fused kernel, on purpose: at any P and algorithm they run
+ * as pairwise passes in the program's own order, per-rank MAX / MIN included (the path unaligned 16-bit buckets
+ * take), and round the running value to 4 (E4M3) or 3 (E5M2) significant bits per combine; the form exists because it
+ * is what the reference's template computes at such an element type. FMI_OP_AVG is valid on both, plain and with the
+ * flag, by its definition: V = f32, store = narrow. fmi_dev_convert (below) moves f32 / f16 / bf16 data into and out
+ * of such buckets. Additive: fmi_abi_version() stays 1. */
 typedef enum {
     FMI_F32 = 0, FMI_F64 = 1, FMI_I32 = 2, FMI_I64 = 3,
     FMI_U32 = 4, FMI_U64 = 5, FMI_I8 = 6, FMI_U8 = 7, FMI_I16 = 8, FMI_U16 = 9,
-    FMI_F16 = 10, FMI_BF16 = 11
+    FMI_F16 = 10, FMI_BF16 = 11, FMI_F8E4M3 = 12, FMI_F8E5M2 = 13
 } fmi_dtype_t;
 
-/* f32 accumulation: a modifier bit on the dtype ARGUMENT of a call, valid only as FMI_F16 | FMI_ACC_F32 or
- * FMI_BF16 | FMI_ACC_F32 (with any other dtype: FMI_ERR_INVALID naming the dtype). The buckets stay 16-bit; a P-way
+/* f32 accumulation: a modifier bit on the dtype ARGUMENT of a call, valid only on FMI_F16, FMI_BF16, FMI_F8E4M3 and
+ * FMI_F8E5M2 (with any other dtype: FMI_ERR_INVALID naming the dtype). The buckets keep their storage type; a P-way
  * program at T | FMI_ACC_F32
  *   1. widens every input element to f32 (exact),
  *   2. runs the SAME program in the SAME order (the bracketing of `alg`) with f32 combines: IEEE round-to-nearest-
  *      even, subnormals kept, no contraction, exactly what the FMI_F32 kernels compute,
- *   3. narrows every value the call STORES to T once (round-to-nearest-even, subnormals kept, NaN stays NaN): the
+ *   3. narrows every value the call STORES to T once (round-to-nearest-even, subnormals kept, NaN stays NaN; for the
+ *      8-bit floats the non-saturating narrowing defined at fmi_dtype_t): the
  *      result of fmi_dev_reduce_tree, every prefix of fmi_dev_scan_peers, every partial fmi_comm_reduce_sendbuf leaves
  *      in a sendbuf, each its own f32 value rounded once.
  * In one line: out = narrow(F32_program(widen(x))). What a gradient bucket that travels in bf16 wants: the plain
@@ -135,10 +163,10 @@ typedef enum {
  * definition by construction, at P * n * 4 bytes of temporaries (+ n * 4 for fmi_dev_reduce_tree's result) in an
  * allocation of the library's own (FMI_ERR_ALLOC if it cannot be had).
  * The communicator calls (fmi_comm_allreduce on paths TREE and DIRECT, _allreduce_host, _reduce, _reduce_sendbuf,
- * _scan) accept it: the wire stays 16-bit and only the shard step changes; every rank passes the same dtype argument,
+ * _scan) accept it: the wire keeps the storage type (16-bit or 8-bit) and only the shard step changes; every rank passes the same dtype argument,
  * as every other argument. FMI_PATH_RCCL with the flag (SUM / PROD) is FMI_ERR_UNSUPPORTED: RCCL's reduction has its
  * own order and rounding. Additive: fmi_abi_version() stays 1, no new symbol. */
-#define FMI_ACC_F32 0x100   /* valid only as FMI_F16 | FMI_ACC_F32 or FMI_BF16 | FMI_ACC_F32 */
+#define FMI_ACC_F32 0x100   /* valid only on FMI_F16, FMI_BF16, FMI_F8E4M3 and FMI_F8E5M2 */
 
 /* Evaluation orders reproduced by the P-way kernels; each is the combine order of one reference
  * collective, so a P-bucket reduction on one device is bit-identical to the distributed one. */
@@ -235,7 +263,10 @@ int fmi_event_elapsed_ms(float* ms, fmi_event_t start, fmi_event_t stop);
  * kernel each); beyond 16 peers or on unaligned buckets they need the f32 temporaries and are not. FMI_OP_AVG at
  * P <= 16 on aligned buckets is capture-safe (one fused kernel); beyond that it is capture-safe exactly where the
  * FMI_OP_SUM call is (the scale runs in place and needs no temporary), and with FMI_ACC_F32 beyond 16 peers or on
- * unaligned buckets it is not. fmi_dev_mean_scale is capture-safe. Beyond 16 peers a call on such buckets
+ * unaligned buckets it is not. fmi_dev_mean_scale and fmi_dev_convert are capture-safe. The 8-bit floats: the pairwise
+ * calls are capture-safe, and so are the FMI_ACC_F32 calls (FMI_OP_AVG with the flag included) at P <= 16 on aligned
+ * buckets (one fused kernel each); PLAIN FMI_F8E4M3 / FMI_F8E5M2 P-way calls at P > 1 run as pairwise passes through
+ * the scratch arena and are not. Beyond 16 peers a call on such buckets
  * is capture-safe exactly where it needs no temporary bucket, which at FMI_TUNE_BLOCKS_ONE_PASS = 1 (the default)
  * is, the same for the six dtypes: FMI_ALG_ALLREDUCE at P <= 31 and P = 32, 48, 64, 80, 96, 112; FMI_ALG_REDUCE at
  * P <= 128; FMI_ALG_SCAN at P <= 143; FMI_ALG_SCAN_LTR at any P; FMI_ALG_REDUCE_LTR at P <= 128, and beyond when
@@ -290,10 +321,19 @@ int fmi_dev_reduce_tree(int op, int dtype, int alg, void* out, const void* const
 
 /* The scale step of FMI_OP_AVG alone, in place: inout[i] = store(fl_V(value(inout[i]) x r_P)), r_P = fl_V(1 / P), as
  * defined at FMI_OP_AVG, for callers who ran FMI_OP_SUM through an exchange of their own. dtype: FMI_F32, FMI_F64,
- * FMI_F16 or FMI_BF16 (anything else, FMI_ACC_F32 included: FMI_ERR_INVALID); P >= 1 (P = 1 leaves the bits
+ * FMI_F16, FMI_BF16, FMI_F8E4M3 or FMI_F8E5M2 (anything else, FMI_ACC_F32 included: FMI_ERR_INVALID); P >= 1 (P = 1 leaves the bits
  * unchanged); any alignment (16-B nontemporal accesses on a 16-B aligned bucket, one element per thread otherwise);
  * n = 0 succeeds. One launch, graph-capturable. */
 int fmi_dev_mean_scale(int dtype, void* inout, size_t n, int P, fmi_stream_t stream);
+
+/* Element-type conversion: dst[i] = narrow_dst(widen_src(src[i])) for i < n. Both dtypes are among FMI_F32, FMI_F16,
+ * FMI_BF16, FMI_F8E4M3, FMI_F8E5M2 (anything else, FMI_ACC_F32 included: FMI_ERR_INVALID). The value goes through f32:
+ * widening is exact, so there is one rounding in all, the narrowing defined at fmi_dtype_t (round-to-nearest-even,
+ * subnormals kept, NaN stays NaN; to the 8-bit floats non-saturating). Equal dtypes: a copy of the bits. dst == src is
+ * allowed at equal element size; otherwise the two must not overlap. Any alignment (16-B nontemporal accesses where
+ * both pointers are 16-B aligned, one element per thread otherwise); n = 0 succeeds. One launch, graph-capturable.
+ * It is FMI_ACC_F32's fallback conversion made public: how f32 / bf16 data gets into an 8-bit float bucket. */
+int fmi_dev_convert(int dst_dtype, void* dst, int src_dtype, const void* src, size_t n, fmi_stream_t stream);
 
 /* Peer-axis inclusive scan of P device buckets: outs[k] = x0 (+) ... (+) xk with the evaluation order
  * of `alg` (FMI_ALG_SCAN or FMI_ALG_SCAN_LTR). Replaces reference PeerToPeer::scan_no_order / scan_ltr
@@ -427,7 +467,10 @@ int fmi_comm_barrier(fmi_comm_t comm, fmi_stream_t stream);
 
 /* ---- synthetic buckets (identical on host and device: SURVEY.md §8d generator) ------------------
  * h = splitmix64(seed ^ ((uint64)peer << 40) ^ i);  f32 = (float)((h >> 40) * 2^-24) * 2 - 1,
- * f64 = (double)((h >> 11) * 2^-53) * 2 - 1,  i32 = (int32)(h >> 32),  i64 = (int64)h. */
+ * f64 = (double)((h >> 11) * 2^-53) * 2 - 1,  i32 = (int32)(h >> 32),  i64 = (int64)h.
+ * The narrow floats take values exact in their storage type: f16 = (h >> 53) * 2^-11 * 2 - 1 (multiples of 2^-10),
+ * bf16 = (h >> 56) * 2^-8 * 2 - 1 (multiples of 2^-7), E4M3 = (h >> 60) * 2^-4 * 2 - 1 (multiples of 2^-3),
+ * E5M2 = (h >> 61) * 2^-3 * 2 - 1 (multiples of 2^-2): all in [-1, 1), each narrowed without rounding. */
 int fmi_dev_fill_synthetic(int dtype, void* buf, size_t n, uint64_t seed, uint32_t peer,
                            fmi_stream_t stream);
 /* Elements [first, first + n) of the same synthetic bucket (i runs from `first`): lets a rank rebuild any
