@@ -1702,7 +1702,7 @@ int allreduce_device(Comm* c, int op, int dtype, int kd, int alg, int path, cons
                     ptrs.in[j] = parts[j];
                     ptrs.out[j] = red + j * shard * esz;
                 }
-                FMI_COMM_RC(launch_fused_allreduce_all_ranks(op, dtype, N, ptrs, shard, s));
+                FMI_COMM_RC(launch_fused_all_ranks(op, dtype, N, ptrs, shard, s));
             } else {
                 for (int r = 0; r < N; ++r)
                     FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red + r * shard * esz, parts.data(), N, r, shard, s));

@@ -410,11 +410,7 @@ int tree_blocked(int op, int dtype, int alg, void* out, const void* const* ins, 
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) ptrs.in[p] = ins[p];
         ptrs.out[0] = out;
-        switch (alg) {
-            case FMI_ALG_ALLREDUCE: return launch_fused_allreduce(op, dtype, P, ptrs, n, rank, s);
-            case FMI_ALG_REDUCE: return launch_fused_reduce(op, dtype, P, ptrs, n, s);
-            default: return launch_fused_reduce_ltr(op, dtype, P, ptrs, n, s);
-        }
+        return launch_fused(alg, op, dtype, P, ptrs, n, rank, s);
     }
     switch (alg) {
         case FMI_ALG_REDUCE_LTR: {
@@ -427,7 +423,7 @@ int tree_blocked(int op, int dtype, int alg, void* out, const void* const* ins, 
                 ptrs.in[0] = acc;
                 for (int j = 0; j < m; ++j) ptrs.in[1 + j] = ins[p + j];
                 ptrs.out[0] = p + m == P ? out : acc;  // elementwise: reading and writing acc in one pass is safe
-                FMI_RC_TRY(launch_fused_reduce_ltr(op, dtype, 1 + m, ptrs, n, s));
+                FMI_RC_TRY(launch_fused(sched::kReduceLtr, op, dtype, 1 + m, ptrs, n, 0, s));
             }
             return FMI_OK;
         }
@@ -465,7 +461,7 @@ int tree_blocked(int op, int dtype, int alg, void* out, const void* const* ins, 
                         PeerPtrs ptrs{};
                         for (int j = 0; j < 2 * B16; ++j) ptrs.in[j] = y[j];
                         ptrs.out[0] = v;
-                        FMI_RC_TRY(launch_fused_allreduce_prefold16(op, dtype, ptrs, n, r % B16, s));
+                        FMI_RC_TRY(launch_fused(sched::kAllreducePrefold16, op, dtype, 2 * B16, ptrs, n, r % B16, s));
                     }
                 } else {
                     FMI_RC_TRY(tree_blocked(op, dtype, alg, v, y.data(), static_cast<int>(y.size()), r % B16, n, s, t));
@@ -526,7 +522,7 @@ int reduce_level(int op, int dtype, void* out, const void* const* vals, int P, s
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) ptrs.in[p] = vals[p];
         ptrs.out[0] = out;
-        return launch_fused_reduce(op, dtype, P, ptrs, n, s);
+        return launch_fused(sched::kReduce, op, dtype, P, ptrs, n, 0, s);
     }
     BlockedScanPtrs ptrs{};
     for (int p = 0; p < P; ++p) ptrs.in[p] = vals[p];
@@ -605,7 +601,7 @@ int allreduce_superblocks(int op, int dtype, void* out, const void* const* ins, 
             PeerPtrs ptrs{};
             for (int b = 0; b < S; ++b) ptrs.in[b] = vals[b];
             ptrs.out[0] = out;
-            rc = launch_fused_allreduce(op, dtype, S, ptrs, n, rank / kAllreduceSuper, s);
+            rc = launch_fused(sched::kAllreduce, op, dtype, S, ptrs, n, rank / kAllreduceSuper, s);
         } else {
             BlockedScanPtrs ptrs{};
             for (int b = 0; b < S; ++b) ptrs.in[b] = vals[b];
@@ -687,7 +683,7 @@ int scan_blocked(int op, int dtype, int alg, void* const* outs, const void* cons
             ptrs.in[p] = ins[p];
             ptrs.out[p] = outs[p];
         }
-        return alg == FMI_ALG_SCAN ? launch_fused_scan(op, dtype, P, ptrs, n, s) : launch_fused_scan_ltr(op, dtype, P, ptrs, n, s);
+        return launch_fused(alg, op, dtype, P, ptrs, n, 0, s);
     }
     auto carry_block = [&](int lo, int m, const void* carry) -> int {
         if (dry) return FMI_OK;
@@ -697,8 +693,7 @@ int scan_blocked(int op, int dtype, int alg, void* const* outs, const void* cons
             ptrs.in[1 + j] = ins[lo + j];
             ptrs.out[1 + j] = outs[lo + j];
         }
-        return alg == FMI_ALG_SCAN ? launch_fused_scan_carry(op, dtype, m + 1, ptrs, n, s)
-                                   : launch_fused_scan_ltr_carry(op, dtype, m + 1, ptrs, n, s);
+        return launch_fused(alg == FMI_ALG_SCAN ? sched::kScanCarry : sched::kScanLtrCarry, op, dtype, m + 1, ptrs, n, 0, s);
     };
     if (alg == FMI_ALG_SCAN_LTR) {
         FMI_RC_TRY(scan_blocked(op, dtype, alg, outs, ins, BL, n, s, t));
@@ -721,7 +716,7 @@ int scan_blocked(int op, int dtype, int alg, void* const* outs, const void* cons
             PeerPtrs r{};
             for (int j = 0; j < BL; ++j) r.in[j] = ins[b * BL + BL - 1 - j];
             r.out[0] = tb;
-            FMI_RC_TRY(launch_fused_reduce(op, dtype, BL, r, n, s));
+            FMI_RC_TRY(launch_fused(sched::kReduce, op, dtype, BL, r, n, 0, s));
         }
         FMI_RC_TRY(scan_blocked(op, dtype, FMI_ALG_SCAN, prefix.data(), totals.data(), B, n, s, t));
     }
@@ -759,7 +754,7 @@ int run_scan_blocked(int op, int dtype, int alg, void* const* outs, const void* 
             c.in[1 + j] = ins[B * BL + j];
             c.out[1 + j] = outs[B * BL + j];
         }
-        return launch_fused_scan_carry(op, dtype, r + 1, c, n, s);
+        return launch_fused(sched::kScanCarry, op, dtype, r + 1, c, n, 0, s);
     }
     TreeTemps count;
     FMI_RC_TRY(scan_blocked(op, dtype, alg, outs, ins, P, n, s, count));
@@ -895,7 +890,7 @@ int reduce_partials(int op, int dtype_arg, void* const* outs, const void* const*
                 ptrs.in[p] = ins[p];
                 ptrs.out[p] = outs[p];
             }
-            return launch_fused_reduce_partials(op, dtype, P, ptrs, n, s);
+            return launch_fused(sched::kReducePartials, op, dtype, P, ptrs, n, 0, s);
         }
         std::vector<int> slot(P);
         for (int p = 0; p < P; ++p) slot[p] = p;  // in place: partial t overwrites input t's temporary
@@ -911,7 +906,7 @@ int reduce_partials(int op, int dtype_arg, void* const* outs, const void* const*
             ptrs.in[p] = ins[p];
             ptrs.out[p] = outs[p];
         }
-        return launch_fused_reduce_partials(op, dtype, P, ptrs, n, s);
+        return launch_fused(sched::kReducePartials, op, dtype, P, ptrs, n, 0, s);
     }
     const sched::HostProgram prog = sched::build_host(sched::kReducePartials, P);
     if (!prog.ok) return fail(FMI_ERR_INVALID, "schedule construction failed");
@@ -1433,10 +1428,10 @@ int fmi_dev_combine(int op, int dtype, void* out, const void* a, const void* b, 
 
 static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const void* const* ins, int P, int rank, size_t n,
                             fmi_stream_t stream) {
-    int dtype = 0;  // the storage dtype from here on; `acc`: the program's values are f32 (FMI_ACC_F32)
-    if (int rc = canonical_dtype(op, dtype_arg, true, P, &dtype)) return rc;
-    const bool acc = accumulates_f32(dtype);
-    dtype = storage_dtype(dtype);
+    int canon = 0;  // the dtype argument in canonical form: what launch_fused takes
+    if (int rc = canonical_dtype(op, dtype_arg, true, P, &canon)) return rc;
+    const bool acc = accumulates_f32(canon);  // the program's values are f32 (FMI_ACC_F32)
+    const int dtype = storage_dtype(canon);
     // FMI_OP_AVG: the SUM program, its result scaled by fl(1 / P) before the one store (include/fmi_dev.h). From here
     // on `op` is the program's op; P = 1 stays the copy.
     const bool avg = op == FMI_OP_AVG && P != 1;
@@ -1477,18 +1472,13 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
         if (int rc = reduce_tree_impl(FMI_OP_SUM, dtype, alg, out, ins, P, rank, n, stream)) return rc;
         return launch_mean_scale(dtype, out, n, P, s);
     }
-    if (acc) dtype |= FMI_ACC_F32;  // launch_fused hands these to the acc32 units
-    if (avg) op = FMI_OP_AVG;       // and these to the mean units: 2 <= P <= 16, aligned
-    if (P >= 2 && aligned && fused_covers_arg(op, dtype, alg, P)) {
-        if (P > sched::max_fused_peers(alg)) return run_tree_blocked(op, dtype, alg, out, order.data(), P, rank, n, s);
+    const int fused_op = avg ? FMI_OP_AVG : op;  // a mean left by now has a fused kernel: 2 <= P <= 16, aligned
+    if (P >= 2 && aligned && fused_covers(fused_op, canon, alg, P)) {
+        if (!fused_has_unit(alg, fused_op, canon, P)) return run_tree_blocked(op, dtype, alg, out, order.data(), P, rank, n, s);
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) ptrs.in[p] = order[p];
         ptrs.out[0] = out;
-        switch (alg) {
-            case FMI_ALG_ALLREDUCE: return launch_fused_allreduce(op, dtype, P, ptrs, n, rank, s);
-            case FMI_ALG_REDUCE: return launch_fused_reduce(op, dtype, P, ptrs, n, s);
-            default: return launch_fused_reduce_ltr(op, dtype, P, ptrs, n, s);
-        }
+        return launch_fused(alg, fused_op, canon, P, ptrs, n, rank, s);
     }
     const sched::HostProgram prog = sched::build_host(alg, P);
     if (!prog.ok) return fail(FMI_ERR_INVALID, "schedule construction failed");
@@ -1500,10 +1490,10 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
 static int scan_peers_impl(int op, int dtype_arg, int alg, void* const* outs, const void* const* ins, int P, size_t n,
                            fmi_stream_t stream) {
     if (int rc = refuse_avg(op, "fmi_dev_scan_peers", "a prefix over the peers has no mean")) return rc;
-    int dtype = 0;  // as in reduce_tree_impl
-    if (int rc = canonical_dtype(op, dtype_arg, true, P, &dtype)) return rc;
-    const bool acc = accumulates_f32(dtype);
-    dtype = storage_dtype(dtype);
+    int canon = 0;  // as in reduce_tree_impl
+    if (int rc = canonical_dtype(op, dtype_arg, true, P, &canon)) return rc;
+    const bool acc = accumulates_f32(canon);
+    const int dtype = storage_dtype(canon);
     if (int rc = check_peer_args(op, dtype, P)) return rc;
     if (alg != FMI_ALG_SCAN && alg != FMI_ALG_SCAN_LTR)
         return fail(FMI_ERR_INVALID, "fmi_dev_scan_peers: alg must be SCAN or SCAN_LTR");
@@ -1522,16 +1512,14 @@ static int scan_peers_impl(int op, int dtype_arg, int alg, void* const* outs, co
             return scan_peers_impl(op, FMI_F32, alg, fo, fi, P, n, stream);
         });
     }
-    if (acc) dtype |= FMI_ACC_F32;  // launch_fused hands these to the acc32 units
-    if (P >= 2 && aligned && fused_covers_arg(op, dtype, alg, P)) {
-        if (P > sched::max_fused_peers(alg)) return run_scan_blocked(op, dtype, alg, outs, ins, P, n, s);
+    if (P >= 2 && aligned && fused_covers(op, canon, alg, P)) {
+        if (!fused_has_unit(alg, op, canon, P)) return run_scan_blocked(op, dtype, alg, outs, ins, P, n, s);
         PeerPtrs ptrs{};
         for (int p = 0; p < P; ++p) {
             ptrs.in[p] = ins[p];
             ptrs.out[p] = outs[p];
         }
-        return alg == FMI_ALG_SCAN ? launch_fused_scan(op, dtype, P, ptrs, n, s)
-                                   : launch_fused_scan_ltr(op, dtype, P, ptrs, n, s);
+        return launch_fused(alg, op, canon, P, ptrs, n, 0, s);
     }
     const sched::HostProgram prog = sched::build_host(alg, P);
     if (!prog.ok) return fail(FMI_ERR_INVALID, "schedule construction failed");

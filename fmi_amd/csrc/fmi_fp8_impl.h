@@ -7,7 +7,8 @@
 // peer (v_cvt_pk_f32_fp8 / _bf8), run the steps on 2-lane f32 vectors (v_pk_add_f32 / v_pk_mul_f32), narrow every
 // stored value into words 2h and 2h + 1 of its output (v_cvt_pk_fp8_f32 / _bf8_f32), h = 0, 1. Loads and stores stay
 // 16 B, the policy (buffer or global accesses, cache bits) is the plain fused kernels'. The < 16-B tail of a bucket
-// goes through the generic one-lane groups (tree_group / scan_group at W = 1).
+// goes through the generic one-lane groups (tree_group / scan_group at W = 1). Launched by fused_one (fmi_fused_impl.h)
+// at element Acc32<T>, T an 8-bit float: op sum, prod or (the three reduce algorithms) the mean.
 #pragma once
 
 #include "fmi_fused_impl.h"
@@ -132,43 +133,6 @@ __global__ void __launch_bounds__(256) fp8_acc_kernel(PeerPtrs ptrs, size_t n, i
         else
             tree_group<Op, T, ALG, P, false, 1, float>(ptrs, 0, first + threadIdx.x);
     }
-}
-
-template <class Op, class T, int ALG, int P>
-void fused_fp8_acc32_one(const PeerPtrs& ptrs, size_t n, int, hipStream_t s) {
-    constexpr bool kScan = sched::stores_all_outputs(ALG);
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(grid_for(n / 16, kFusedBlock), kFusedGridCap));
-    const size_t lds = fused_lds_bytes(P, kFusedBlock * 16);
-    fp8_acc_kernel<Op, T, ALG, P, kScan><<<grid, kFusedBlock, lds, s>>>(ptrs, n, fused_policy(kScan, P));
-}
-
-template <class Op, class T, int ALG, int... I>
-constexpr std::array<FusedFn, sizeof...(I)> fused_fp8_acc32_table(std::integer_sequence<int, I...>) {
-    return {&fused_fp8_acc32_one<Op, T, ALG, I + 2>...};
-}
-
-// op: FMI_OP_SUM, FMI_OP_PROD or (the three reduce algorithms) FMI_OP_AVG; dtype: the storage dtype.
-template <int ALG>
-int launch_fused_fp8_acc32_family(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    if (P < 2 || P > sched::kMaxFusedPeers)
-        return fail(FMI_ERR_INVALID, "fused f32-accumulating kernel needs 2 <= P <= 16, got " + std::to_string(P));
-    auto launch = [&]<class Op, class T>() -> int {
-        static constexpr auto table = fused_fp8_acc32_table<Op, T, ALG>(std::make_integer_sequence<int, sched::kMaxFusedPeers - 1>{});
-        table[P - 2](ptrs, n, 0, s);
-        return check_launch("fused f32-accumulating 8-bit float kernel launch");
-    };
-    return with_dtype<kTierFp8>(dtype, [&]<class T>() -> int {
-        switch (op) {
-            case FMI_OP_SUM: return launch.template operator()<OpSum, T>();
-            case FMI_OP_PROD: return launch.template operator()<OpProd, T>();
-            case FMI_OP_AVG:
-                if constexpr (!sched::stores_all_outputs(ALG))
-                    return launch.template operator()<OpAvg, T>();
-                else
-                    return fail(FMI_ERR_INVALID, "FMI_OP_AVG: no mean for algorithm " + std::to_string(ALG));
-            default: return fail(FMI_ERR_INVALID, "f32 accumulation: max / min are selections and run the plain kernels");
-        }
-    });
 }
 
 }  // namespace fmi::dev

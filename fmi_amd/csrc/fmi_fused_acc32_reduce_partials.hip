@@ -4,7 +4,5 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_acc32_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused_acc32_family<sched::kReducePartials>(op, dtype, P, ptrs, n, s);
-}
+template FusedUnit fused_unit<sched::kReducePartials, kFusedAcc32, 2, sched::kMaxFusedPeers>;
 }  // namespace fmi::dev

@@ -3,7 +3,5 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_avg_allreduce(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused_avg_family<sched::kAllreduce>(dtype, P, ptrs, n, s);
-}
+template FusedUnit fused_unit<sched::kAllreduce, kFusedAvg, 2, sched::kMaxFusedPeers>;
 }  // namespace fmi::dev

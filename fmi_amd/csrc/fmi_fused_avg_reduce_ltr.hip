@@ -3,7 +3,5 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_avg_reduce_ltr(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused_avg_family<sched::kReduceLtr>(dtype, P, ptrs, n, s);
-}
+template FusedUnit fused_unit<sched::kReduceLtr, kFusedAvg, 2, sched::kMaxFusedPeers>;
 }  // namespace fmi::dev

@@ -3,7 +3,5 @@
 #include "fmi_fp8_impl.h"
 
 namespace fmi::dev {
-int launch_fused_fp8_acc32_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused_fp8_acc32_family<sched::kScan>(op, dtype, P, ptrs, n, s);
-}
+template FusedUnit fused_unit<sched::kScan, kFusedFp8Acc32, 2, sched::kMaxFusedPeers>;
 }  // namespace fmi::dev

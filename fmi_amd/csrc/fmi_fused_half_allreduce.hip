@@ -4,9 +4,6 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_half_allreduce(int op, int dtype, bool rank_aware, int P, const PeerPtrs& ptrs, size_t n, int rank,
-                                hipStream_t s) {
-    if (rank_aware) return launch_fused<sched::kAllreduce, true, 2, sched::kMaxFusedPeers, kTierHalf>(op, dtype, P, ptrs, n, rank, s);
-    return launch_fused<sched::kAllreduce, false, 2, sched::kMaxFusedPeers, kTierHalf>(op, dtype, P, ptrs, n, rank, s);
-}
+template FusedUnit fused_unit<sched::kAllreduce, kFusedHalf, 2, sched::kMaxFusedPeers>;
+template FusedUnit fused_unit<sched::kAllreduce, kFusedHalf, 2, sched::kMaxFusedPeers, kRankPicked>;
 }  // namespace fmi::dev

@@ -4,8 +4,5 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_half_allreduce_wide_f16(int op, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s) {
-    return launch_fused<sched::kAllreduce, true, sched::kMaxFusedPeers + 1, sched::kMaxFusedAllreducePeers, kTierF16>(
-        op, FMI_F16, P, ptrs, n, rank, s);
-}
+template FusedUnit fused_unit<sched::kAllreduce, kFusedF16, sched::kMaxFusedPeers + 1, sched::kMaxFusedAllreducePeers, kRankPicked>;
 }  // namespace fmi::dev

@@ -3,7 +3,5 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_half_scan_ltr_carry(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused<sched::kScanLtrCarry, false, 2, sched::kMaxFusedPeers, kTierHalf>(op, dtype, P, ptrs, n, 0, s);
-}
+template FusedUnit fused_unit<sched::kScanLtrCarry, kFusedHalf, 2, sched::kMaxFusedPeers>;
 }  // namespace fmi::dev

@@ -2,7 +2,5 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_half_scan_ltr_wide(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused<sched::kScanLtr, false, sched::kMaxFusedPeers + 1, sched::kMaxFusedScanPeers, kTierHalf>(op, dtype, P, ptrs, n, 0, s);
-}
+template FusedUnit fused_unit<sched::kScanLtr, kFusedHalf, sched::kMaxFusedPeers + 1, sched::kMaxFusedScanPeers>;
 }  // namespace fmi::dev

@@ -4,13 +4,7 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused<sched::kReduce, false>(op, dtype, P, ptrs, n, 0, s);
-}
-int launch_fused_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused<sched::kReduceLtr, false>(op, dtype, P, ptrs, n, 0, s);
-}
-int launch_fused_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    return launch_fused<sched::kReducePartials, false>(op, dtype, P, ptrs, n, 0, s);
-}
+template FusedUnit fused_unit<sched::kReduce, kFusedCore, 2, sched::kMaxFusedPeers>;
+template FusedUnit fused_unit<sched::kReduceLtr, kFusedCore, 2, sched::kMaxFusedPeers>;
+template FusedUnit fused_unit<sched::kReducePartials, kFusedCore, 2, sched::kMaxFusedPeers>;
 }  // namespace fmi::dev

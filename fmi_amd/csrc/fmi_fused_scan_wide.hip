@@ -4,9 +4,6 @@
 #include "fmi_fused_impl.h"
 
 namespace fmi::dev {
-int launch_fused_scan_wide(int op, int dtype, int alg, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {
-    constexpr int LO = sched::kMaxFusedPeers + 1, HI = sched::kMaxFusedScanPeers;
-    return alg == sched::kScan ? launch_fused<sched::kScan, false, LO, HI>(op, dtype, P, ptrs, n, 0, s)
-                               : launch_fused<sched::kScanLtr, false, LO, HI>(op, dtype, P, ptrs, n, 0, s);
-}
+template FusedUnit fused_unit<sched::kScan, kFusedCore, sched::kMaxFusedPeers + 1, sched::kMaxFusedScanPeers>;
+template FusedUnit fused_unit<sched::kScanLtr, kFusedCore, sched::kMaxFusedPeers + 1, sched::kMaxFusedScanPeers>;
 }  // namespace fmi::dev

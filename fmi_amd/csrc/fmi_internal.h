@@ -77,26 +77,42 @@ inline int refuse_avg(int op, const char* who, const char* why) {
     return fail(FMI_ERR_INVALID, std::string(who) + ": op " + std::to_string(op) + " (FMI_OP_AVG) is not valid here: " + why);
 }
 
-// Which (op, dtype, algorithm, P) have a single-pass kernel (fused, or built from fused blocks): the core dtypes and
-// the 16-bit floats, everywhere. The 8/16-bit integers take run_program_stepwise. No (op, algorithm, P) of the
-// 16-bit floats is held back: none of their kernels needs scratch memory, which is what `op` is
-// here to decide should one ever do.
-// `alg`: a sched::Alg (the C-ABI's fmi_alg_t values are its first five).
-inline bool fused_covers(int op, int dtype, int alg, int P) {
-    (void)op, (void)alg, (void)P;
-    return is_core_dtype(dtype) || is_half_dtype(dtype);
-}
-// The same question for a dtype ARGUMENT in canonical form: the 8-bit floats have fused kernels only with FMI_ACC_F32
-// (sum / prod / the mean, 2 <= P <= 16; the callers send P > 16 and unaligned buckets to the f32 fallback first).
-inline bool fused_covers_arg(int op, int dtype_arg, int alg, int P) {
+// The variants of a fused P-way launch: which elements and ops a call's kernels are instantiated for. Every translation
+// unit of fused kernels holds one variant of one algorithm over one peer range (fused_unit below).
+enum FusedVariant : int {
+    kFusedNone = -1,  // no fused kernel: pairwise passes in the program's order (run_program_stepwise)
+    kFusedCore,       // f32 f64 i32 i64, the four ops
+    kFusedHalf,       // f16 bf16, the four ops
+    kFusedF16,        // one of the two: the largest half programs (allreduce, P = 17..31) build one dtype per
+    kFusedBF16,       // translation unit
+    kFusedAcc32,      // FMI_ACC_F32 over f16 / bf16 (element Acc32<T>): sum, prod
+    kFusedFp8Acc32,   // FMI_ACC_F32 over the 8-bit floats (fp8_acc_kernel): sum, prod and, on a reduction result, the mean
+    kFusedAvg,        // FMI_OP_AVG over f32 f64 f16 bf16 and Acc32 of the last two
+};
+// The variant of a call. op: an fmi_op_t; dtype_arg: in canonical form (canonical_dtype). The 8-bit floats are fused
+// only with the flag (their plain P-way programs are out of scope on purpose); the 8/16-bit and unsigned integers never.
+inline int fused_variant(int op, int dtype_arg) {
     const int st = storage_dtype(dtype_arg);
-    if (is_fp8_dtype(st)) return accumulates_f32(dtype_arg) && P <= sched::kMaxFusedPeers;
-    return fused_covers(op, st, alg, P);
+    if (is_fp8_dtype(st)) return accumulates_f32(dtype_arg) ? kFusedFp8Acc32 : kFusedNone;
+    if (op == FMI_OP_AVG) return st == FMI_F32 || st == FMI_F64 || is_half_dtype(st) ? kFusedAvg : kFusedNone;
+    if (accumulates_f32(dtype_arg)) return is_half_dtype(st) ? kFusedAcc32 : kFusedNone;
+    return is_half_dtype(st) ? kFusedHalf : is_core_dtype(st) ? kFusedCore : kFusedNone;
+}
+// Whether launch_fused (below) has a unit for the call (fmi_fused.hip, from the one table of units it dispatches on).
+// alg: a sched::Alg (the C-ABI's fmi_alg_t values are its first five).
+bool fused_has_unit(int alg, int op, int dtype_arg, int P);
+// Which (op, dtype argument, algorithm, P) have a single-pass kernel: a fused unit, or for the plain variants at any
+// P beyond theirs a program built from fused blocks (the callers send P > 16 and unaligned buckets of the other
+// variants to their fallbacks first). No (op, algorithm, P) of the 16-bit floats is held back: none of their
+// kernels needs scratch memory.
+inline bool fused_covers(int op, int dtype_arg, int alg, int P) {
+    const int var = fused_variant(op, dtype_arg);
+    return var == kFusedCore || var == kFusedHalf || fused_has_unit(alg, op, dtype_arg, P);
 }
 
 // Dispatch tiers of with_dtype. The fused launch tables are built per tier: the core tier in the translation
-// units that always held them, the half tier in fmi_fused_half_*.hip (launch_fused routes there), so
-// core + half is what a fused launch serves and ALL what the pairwise family serves.
+// units that always held them, the half tier in fmi_fused_half_*.hip, so core + half is what a plain fused
+// launch serves and ALL what the pairwise family serves.
 inline constexpr int kTierCore = 0;  // f32 f64 i32 i64
 inline constexpr int kTierAll = 1;   // every fmi_dtype_t
 inline constexpr int kTierHalf = 2;  // f16 bf16 alone
@@ -165,64 +181,37 @@ inline size_t dtype_size(int dtype) {
 
 inline bool is_float(int dtype) { return dtype == FMI_F32 || dtype == FMI_F64 || is_half_dtype(dtype) || is_fp8_dtype(dtype); }
 
-// Fused single-pass launches (P in [2, kMaxFusedPeers], all pointers 16-B aligned). One function per
-// algorithm family, each defined in its own translation unit so the ~1.2k instantiations build in
-// parallel. Return 0 or a negative fmi_status_t.
-int launch_fused_allreduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
-// a 16-peer allreduce block whose peers all pre-fold a partner: ins[0..16) the block, ins[16..32) the
-// partners; out[0] = the value of block peer `rank` (< 16)
-int launch_fused_allreduce_prefold16(int op, int dtype, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
-// allreduce_no_order's value for every peer at once (outs[r] for r < P), float max / min only
-int launch_fused_allreduce_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
+// Every fused single-pass launch (fmi_fused.hip; all pointers 16-B aligned): classifies the call (fused_variant),
+// checks op and P against the variant's kernels at `alg`, applies the allreduce's host-side pointer permutations and
+// calls the one translation unit that holds the instantiations. Returns 0 or a negative fmi_status_t.
+// alg: a sched::Alg. op: an fmi_op_t, FMI_OP_AVG included. dtype_arg: in canonical form. rank: the allreduces' alone.
+//   kAllreduce (P <= 31), kReduce, kReduceLtr: ptrs.out[0] = the result (of peer `rank`);
+//   kAllreducePrefold16 (P = 32): a 16-peer allreduce block whose peers all pre-fold a partner: in[0..16) the block,
+//     in[16..32) the partners; out[0] = the value of block peer `rank` (< 16);
+//   kReducePartials: reduce_no_order with every (transformed) peer's final sendbuf stored, ptrs.out[t] for t < P;
+//   kScan, kScanLtr (P <= 31): ptrs.out[p] for p < P;
+//   kScanCarry, kScanLtrCarry: blocks of a scan beyond 16 peers, ptrs.in[0] is the carry, out[0] unused.
+int launch_fused(int alg, int op, int dtype_arg, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
+// allreduce_no_order's value for every peer at once (outs[r] for r < P <= 16), float max / min only
+int launch_fused_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // float max / min: which operand is kept on a tie (±0) or a NaN depends on the order, so every peer of an
 // allreduce can end with different bits
 inline bool order_sensitive(int op, int dtype) { return is_float(dtype) && (op == FMI_OP_MAX || op == FMI_OP_MIN); }
-// allreduce for P = 17..31 (the pre-folded programs), reached through launch_fused_allreduce
-int launch_fused_allreduce_wide(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
-int launch_fused_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// reduce_no_order with every (transformed) peer's final sendbuf stored: ptrs.out[t] for t < P
-int launch_fused_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// The same for any P and any alignment / dtype (fused kernel where it applies, pairwise passes otherwise):
+// Whose value the launch of an allreduce program stores.
+inline constexpr int kRankZero = 0;    // rank 0's expression: every rank's where no rank changes the bits, or the caller permuted the pointers
+inline constexpr int kRankPicked = 1;  // the `rank` argument's: the rank-selecting kernel where the rank can change bits (float max / min)
+inline constexpr int kRankEvery = 2;   // every rank's, out[r] for r < P: the scan kernel over the program, float max / min only
+// One translation unit's fused kernels: algorithm ALG, variant VAR (a FusedVariant), P in [LO, HI]. Declared here for
+// the dispatcher, defined in fmi_fused_impl.h and explicitly instantiated by exactly one fmi_fused_*.hip each (so the
+// ~3,800 instantiations build in parallel), which makes a unit that launch_fused names but no file builds an
+// undefined symbol when the library is linked. Arguments as launch_fused's, already checked by it.
+using FusedUnit = int(int op, int dtype_arg, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
+template <int ALG, int VAR, int LO, int HI, int RANKS = kRankZero>
+FusedUnit fused_unit;
+// kReducePartials for any P and any alignment / dtype (fused kernel where it applies, pairwise passes otherwise):
 // outs[t] = the value transformed peer t of reduce_no_order holds in its sendbuf at the end
 // (src/comm/PeerToPeer.cpp:66-78); ins in transformed order. Defined in fmi_dev.hip.
 int reduce_partials(int op, int dtype, void* const* outs, const void* const* ins, int P, size_t n, hipStream_t s);
-int launch_fused_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// The 16-bit float instantiations of the launches above (fused_covers), each family in a translation unit of its
-// own (fmi_fused_half_*.hip). launch_fused's core tier hands every 16-bit float launch to launch_fused_half
-// (fmi_fused_half.hip), which picks the unit by (alg, P); launch_fused_allreduce_all_ranks and the one-pass
-// launches below route to theirs themselves.
-// rank_aware: the rank-selecting allreduce (float max / min at P != 2^k).
-int launch_fused_half(int alg, bool rank_aware, int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, int rank,
-                      hipStream_t s);
-// FMI_ACC_F32 (dtype = storage dtype | FMI_ACC_F32, op sum or prod, 2 <= P <= 16): launch_fused hands these to
-// launch_fused_acc32 (fmi_fused_acc32.hip), which picks the family's translation unit (fmi_fused_acc32_*.hip); the
-// units take the storage dtype.
-int launch_fused_acc32(int alg, int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_acc32_allreduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_acc32_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_acc32_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_acc32_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_acc32_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_acc32_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// The same for the 8-bit floats (dtype = FMI_F8E4M3 / FMI_F8E5M2 | FMI_ACC_F32; op sum, prod or, at the three reduce
-// algorithms, FMI_OP_AVG; 2 <= P <= 16): launch_fused hands these to launch_fused_fp8_acc32 (fmi_fused_fp8_acc32.hip),
-// which picks the family's translation unit (fmi_fused_fp8_acc32_*.hip); the units take the storage dtype.
-int launch_fused_fp8_acc32(int alg, int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_fp8_acc32_allreduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_fp8_acc32_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_fp8_acc32_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_fp8_acc32_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_fp8_acc32_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_fp8_acc32_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// FMI_OP_AVG at 2 <= P <= 16 (alg: one of the three reduce algorithms; dtype: a float storage dtype, with FMI_ACC_F32
-// where the values are f32): launch_fused hands these to launch_fused_avg (fmi_fused_avg.hip), which picks the
-// algorithm's translation unit (fmi_fused_avg_*.hip).
-int launch_fused_avg(int alg, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_avg_allreduce(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_avg_reduce(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_avg_reduce_ltr(int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // The mean's scale step alone (fmi_scale.hip), in place, any alignment: inout[i] = store(fl_V(value(inout[i]) * fl_V(1 / P))).
 // dtype: one of the six float dtypes.
 int launch_mean_scale(int dtype, void* inout, size_t n, int P, hipStream_t s);
@@ -233,27 +222,6 @@ int launch_narrow_f32(int dtype, void* dst, const float* src, size_t n, hipStrea
 // fmi_dev_convert: dst[i] = narrow_dst(widen_src(src[i])) between any two of f32 / f16 / bf16 / E4M3 / E5M2 (equal
 // dtypes: the bits copied), one launch, any alignment, dst == src allowed at equal element size.
 int launch_convert(int dst_dtype, void* dst, int src_dtype, const void* src, size_t n, hipStream_t s);
-int launch_fused_half_allreduce(int op, int dtype, bool rank_aware, int P, const PeerPtrs& ptrs, size_t n, int rank,
-                                hipStream_t s);
-int launch_fused_half_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_reduce(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_scan(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_reduce_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_reduce_partials(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_scan_ltr(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_scan_carry(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_scan_ltr_carry(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// P = 17..31 (one dtype per translation unit) and the 32-input pre-fold block
-int launch_fused_half_allreduce_wide_f16(int op, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
-int launch_fused_half_allreduce_wide_bf16(int op, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
-int launch_fused_half_prefold16(int op, int dtype, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_scan_wide(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_half_scan_ltr_wide(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// scans for P = 17..31 (alg = sched::kScan or kScanLtr), reached through the two launches above
-int launch_fused_scan_wide(int op, int dtype, int alg, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-// Blocks of a scan beyond 16 peers (sched::kScanCarry / kScanLtrCarry): ptrs.in[0] is the carry, out[0] unused.
-int launch_fused_scan_carry(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
-int launch_fused_scan_ltr_carry(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s);
 // scan_no_order over B full blocks of 16 peers (2 <= B <= kMaxOnePassScanBlocks, P = 32..143) in one pass: every input read
 // once, all 16 B outputs written (fmi_fused_scan_blocked.hip); a ragged last block is left to the caller.
 inline constexpr int kMaxOnePassScanBlocks = 8;

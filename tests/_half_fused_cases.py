@@ -7,7 +7,7 @@ ALLREDUCE_P = [17, 24, 31, 32, 64, 48, 80, 33, 100, 128]
 SCAN_P = [17, 31, 32, 48, 100, 143, 144]
 # further P the GPU file runs outside the four tables: both modes of FMI_TUNE_BLOCKS_ONE_PASS, the policy test,
 # the communicator tests and the captured graph
-EXTRA = {"allreduce": [20], "allreduce_ltr": [4], "scan": [33, 64], "scan_ltr": [4], "reduce": [3, 8, 40], "ltr": []}
+EXTRA = {"allreduce": [20], "allreduce_ltr": [4], "scan": [33, 64], "scan_ltr": [4, 32], "reduce": [3, 8, 40], "ltr": []}
 
 extra_ops_at = {"ltr": 5, "reduce": 31, "allreduce": 24, "scan": 31}  # the one P per family that also runs prod / min
 

@@ -182,7 +182,7 @@ def test_kernel_schedules_match_oracle(P):
 
 def test_allreduce_power_of_two_is_xor_symmetric():
     """For P = 2^k the value peer r holds is rank 0's expression over inputs x[p ^ r], operand order
-    included: what lets fmi_fused_allreduce.hip run the rank-0 kernel over permuted pointers."""
+    included: what lets launch_fused (fmi_fused.hip) run the rank-0 kernel over permuted pointers."""
     for P in (2, 4, 8, 16, 32, 64, 128, 256):
         e0 = fmi_amd.schedule_expr(Alg.ALLREDUCE, P, 0)
         for r in range(P):

@@ -156,12 +156,15 @@ def test_scan_wide_every_output(device, kind, P):
 @pytest.mark.parametrize("kind", H.KINDS)
 def test_blocked_launches_and_one_pass(blocks_one_pass, kind):
     """P = 48 allreduce and P = 33 / 64 scan in both modes: the block launches run the fused carry programs, the
-    32-input pre-fold block and the 16-peer reduce over arena temps."""
+    32-input pre-fold block and the 16-peer reduce over arena temps. scan_ltr at P = 32: its block launches continue
+    the chain from a carry over 15 peers and then over 1, the largest and the smallest program of the chain-carry
+    unit (n = 4099: whole 16-B lane groups and a ragged tail); one pass is the chain kernel."""
     for op in ("sum", "max"):
         for n in WIDE_SIZES:
             run_allreduce(kind, op, n, 48, 24, f"allreduce one_pass={blocks_one_pass}")
             for P in (33, 64):
                 run_scan(Alg.SCAN, kind, op, n, P, 25, f"scan one_pass={blocks_one_pass}")
+        run_scan(Alg.SCAN_LTR, kind, op, 4099, 32, 21, f"scan_ltr one_pass={blocks_one_pass}")
 
 
 @pytest.mark.parametrize("kind", H.KINDS)
