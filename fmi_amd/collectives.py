@@ -81,6 +81,27 @@ class HipEngine:
         _lib.call("fmi_dev_reduce_tree", int(op), dtype, int(alg), out.data_ptr(), ptrs, len(ins), rank,
                   out.numel(), self._stream())
 
+    def reduce_tree_scaled(self, alg: Alg, out: torch.Tensor, ins: Sequence[torch.Tensor], in_scales: torch.Tensor,
+                           out_scale: Optional[torch.Tensor] = None, amax: Optional[torch.Tensor] = None,
+                           rank: int = 0) -> None:
+        """The scaled sum of float8 tensors (fmi_dev_reduce_tree_scaled): in_scales holds one f32 scale per input,
+        out_scale and amax one f32 each, all on the device; `out` is a tensor of the inputs' dtype or of float32."""
+        import ctypes
+        dtype = _dtype(ins[0])
+        if dtype not in (DType.F8E4M3, DType.F8E5M2):
+            raise TypeError(f"reduce_tree_scaled needs float8_e4m3fn or float8_e5m2 inputs, got {ins[0].dtype}")
+        if any(t.dtype != ins[0].dtype or t.numel() != out.numel() or not t.is_contiguous() for t in ins):
+            raise ValueError("reduce_tree_scaled: contiguous inputs of one dtype and of out's length")
+        if out.dtype not in (ins[0].dtype, torch.float32) or not out.is_contiguous():
+            raise ValueError("reduce_tree_scaled: `out` is a contiguous tensor of the inputs' dtype or of float32")
+        for name, t, k in (("in_scales", in_scales, len(ins)), ("out_scale", out_scale, 1), ("amax", amax, 1)):
+            if t is not None and (t.dtype != torch.float32 or t.numel() < k or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError(f"reduce_tree_scaled: {name} must be a contiguous float32 device tensor of >= {k} element(s)")
+        ptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
+        _lib.call("fmi_dev_reduce_tree_scaled", int(Op.SUM), int(dtype), int(alg), int(_dtype(out)), out.data_ptr(), ptrs,
+                  in_scales.data_ptr(), out_scale.data_ptr() if out_scale is not None else None,
+                  amax.data_ptr() if amax is not None else None, len(ins), rank, out.numel(), self._stream())
+
     def fill_synthetic(self, t: torch.Tensor, seed: int, peer: int) -> None:
         _lib.call("fmi_dev_fill_synthetic", int(_dtype(t)), t.data_ptr(), t.numel(), seed, peer, self._stream())
 

@@ -18,7 +18,7 @@ import numpy as np
 
 from ._lib import Timeout  # noqa: F401 - FMI_ERR_TIMEOUT, the reference's FMI::Utils::Timeout
 
-from .device import Alg, Bucket, Op, _sptr, acc_dtype, dtype_of, itemsize_of
+from .device import Alg, Bucket, DType, Op, _f32_word, _sptr, acc_dtype, dtype_of, itemsize_of
 
 ID_BYTES = 128
 
@@ -126,6 +126,22 @@ class Comm:
         arg = acc_dtype(send.dtype, accumulate_f32)
         _lib.call("fmi_comm_allreduce", self.handle, int(op), arg, int(alg), int(path), _p(send), _p(recv), send.n,
                   _sptr(stream))
+
+    def allreduce_scaled(self, send: Bucket, in_scale: Bucket, recv: Bucket, out_scale: Optional[Bucket] = None,
+                         amax: Optional[Bucket] = None, ordered: bool = False, stream=None) -> None:
+        """The sharded allreduce of scaled F8E4M3 / F8E5M2 buckets (fmi_comm_allreduce_scaled, path TREE): rank r's
+        `send` times its own `in_scale` in f32, the f32 sum over the ranks in the reference's order, times `out_scale`,
+        into `recv` (the inputs' dtype or F32) on every rank; `amax` ends as the largest |sum| over the whole bucket,
+        folded into what it held, the same on every rank. The wire carries the 8-bit bytes and one scale per rank.
+        in_scale / out_scale / amax are one-element F32 buckets; out_scale holds the same value on every rank."""
+        if send.dtype not in (DType.F8E4M3, DType.F8E5M2):
+            raise ValueError(f"allreduce_scaled needs an F8E4M3 or F8E5M2 send bucket, got {DType(send.dtype).name}")
+        if recv.n != send.n or recv.dtype not in (send.dtype, DType.F32):
+            raise ValueError("allreduce_scaled: `recv` must hold send's length in its dtype or in F32")
+        alg = Alg.REDUCE_LTR if ordered else Alg.ALLREDUCE
+        _lib.call("fmi_comm_allreduce_scaled", self.handle, int(Op.SUM), int(send.dtype), int(alg), int(recv.dtype),
+                  _p(send), _f32_word(in_scale, "in_scale"), _p(recv), _f32_word(out_scale, "out_scale"),
+                  _f32_word(amax, "amax"), send.n, _sptr(stream))
 
     def window(self, n: int, dtype) -> Bucket:
         """A symmetric window bucket for Path.DIRECT (collective: every rank, same n and dtype). Release it

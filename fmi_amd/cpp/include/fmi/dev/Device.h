@@ -330,6 +330,33 @@ inline void convert(Bucket<D>& dst, const Bucket<S>& src, fmi_stream_t stream = 
     check(fmi_dev_convert(dtype_of<D>(), dst.data(), dtype_of<S>(), src.data(), src.size(), stream), "fmi_dev_convert");
 }
 
+// The scaled sum of 8-bit float buckets (fmi_dev_reduce_tree_scaled): every input times its own scale in float, the
+// float SUM program of `alg` (FMI_ALG_ALLREDUCE / _REDUCE / _REDUCE_LTR, `rank` as in fmi_dev_reduce_tree), the largest
+// |sum| folded into *amax, the sum times *out_scale stored once: into a bucket of the inputs' type (non-saturating
+// narrowing) or a Bucket<float>. in_scales holds one scale per input; out_scale and amax (one float each) may be
+// nullptr: 1 and "not wanted". All of them live on the device, so a captured graph replays with new scales.
+template <class A, class O>
+inline void reduce_tree_scaled(int alg, Bucket<O>& out, const std::vector<const Bucket<A>*>& ins, const Bucket<float>& in_scales,
+                               const Bucket<float>* out_scale = nullptr, Bucket<float>* amax = nullptr, int rank = 0,
+                               fmi_stream_t stream = nullptr) {
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>,
+                  "reduce_tree_scaled: Dev::float8_e4m3 or Dev::float8_e5m2 inputs");
+    static_assert(std::is_same_v<O, A> || std::is_same_v<O, float>, "reduce_tree_scaled: the output is of the inputs' type or float");
+    if (ins.empty() || ins.size() > static_cast<std::size_t>(std::numeric_limits<int>::max()))
+        throw std::runtime_error("Dev::reduce_tree_scaled: need at least one input bucket");
+    std::vector<const void*> ptrs;
+    for (const Bucket<A>* b : ins) {
+        if (!b || b->size() != out.size()) throw std::runtime_error("Dev::reduce_tree_scaled: size mismatch");
+        ptrs.push_back(b->data());
+    }
+    if (in_scales.size() < ins.size() || (out_scale && out_scale->size() < 1) || (amax && amax->size() < 1))
+        throw std::runtime_error("Dev::reduce_tree_scaled: one scale per input, one element for out_scale and amax");
+    check(fmi_dev_reduce_tree_scaled(FMI_OP_SUM, dtype_of<A>(), alg, dtype_of<O>(), out.data(), ptrs.data(), in_scales.data(),
+                                     out_scale ? out_scale->data() : nullptr, amax ? amax->data() : nullptr,
+                                     static_cast<int>(ins.size()), rank, out.size(), stream),
+          "fmi_dev_reduce_tree_scaled");
+}
+
 // Untyped device scratch used by the channel algorithms for temporaries of device-resident buckets.
 class Scratch {
 public:

@@ -1302,8 +1302,8 @@ struct KernelTiming {
 
 struct Comm {
     // 0-3: collective scratch; 4-7 and 16-17: host-pipeline chunk slots (in / out x HostPipe::kDepth);
-    // 8-15: pipelined-allreduce slots (2 x 4)
-    static constexpr int kSlots = 18;
+    // 8-15: pipelined-allreduce slots (2 x 4); 18: the scaled allreduce's words (N scales, N amax words, this rank's)
+    static constexpr int kSlots = 19;
     std::unique_ptr<Transport> t;
     std::mutex mu;
     KernelTiming timing;
@@ -1731,6 +1731,57 @@ int allreduce_device(Comm* c, int op, int dtype, int kd, int alg, int path, cons
     return FMI_OK;
 }
 
+// fmi_comm_allreduce_scaled (include/fmi_dev.h): the sharded allreduce on path TREE, unpipelined, over scaled 8-bit
+// float buckets. The input shards travel as bytes on the padded shard grid; the shard kernel runs on the shard's TRUE
+// length (zero padding times an infinite scale would be a NaN in amax), so what lies beyond it in `red` is never
+// computed and never reaches recv, which takes the first n elements only.
+int allreduce_scaled_device(Comm* c, int dtype, int alg, int out_dtype, const void* send, const float* in_scale, void* recv,
+                            const float* out_scale, float* amax, size_t n, hipStream_t s) {
+    const int N = c->t->n();
+    if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE))  // the P = 1 form: not a copy
+        return reduce_tree_scaled(dtype, alg, out_dtype, recv, &send, in_scale, out_scale, amax, 1, 0, n, s);
+    const size_t osz = dtype_size(out_dtype);  // the inputs' element size is 1
+    const size_t shard = shard_elems(n, N);
+    const size_t padded = shard * N;
+    char* words = nullptr;
+    FMI_COMM_RC(c->scratch(18, (2 * static_cast<size_t>(N) + 1) * sizeof(float), s, &words));
+    float* scales = reinterpret_cast<float*>(words);
+    uint32_t* shard_amax = reinterpret_cast<uint32_t*>(words) + N;
+    uint32_t* mine = shard_amax + N;
+    FMI_COMM_RC(c->t->all_gather(reinterpret_cast<const char*>(in_scale), words, sizeof(float), s));
+    if (amax) FMI_COMM_HIP(hipMemsetAsync(mine, 0, sizeof(uint32_t), s));
+    const char* src = nullptr;
+    FMI_COMM_RC(padded_source(c, n, padded, 1, send, s, &src));
+    char* staging = nullptr;
+    char* red = nullptr;
+    FMI_COMM_RC(c->scratch(1, padded, s, &staging));
+    FMI_COMM_RC(c->scratch(2, shard * osz, s, &red));
+    FMI_COMM_RC(c->t->all_to_all(src, staging, shard, s));
+    const size_t len = Transport::span(c->t->rank(), shard, n);  // elements of my shard
+    if (len) {
+        std::vector<const void*> parts(N);
+        for (int j = 0; j < N; ++j) parts[j] = staging + j * shard;
+        FMI_COMM_RC(c->timing.begin(s));
+        FMI_COMM_RC(reduce_tree_scaled(dtype, alg, out_dtype, red, parts.data(), scales, out_scale,
+                                       amax ? reinterpret_cast<float*>(mine) : nullptr, N, 0, len, s));
+        FMI_COMM_RC(c->timing.end(s));
+    }
+    if (padded == n) {
+        FMI_COMM_RC(c->t->all_gather(red, static_cast<char*>(recv), shard * osz, s));
+    } else {
+        char* out = nullptr;
+        FMI_COMM_RC(c->scratch(3, padded * osz, s, &out));
+        FMI_COMM_RC(c->t->all_gather(red, out, shard * osz, s));
+        FMI_COMM_RC(device_copy(recv, out, n * osz, s));
+    }
+    if (amax) {
+        // every owner's shard amax, then one fold with what *amax held: the same word on every rank
+        FMI_COMM_RC(c->t->all_gather(reinterpret_cast<const char*>(mine), reinterpret_cast<char*>(shard_amax), sizeof(uint32_t), s));
+        FMI_COMM_RC(launch_amax_fold(amax, shard_amax, N, s));
+    }
+    return FMI_OK;
+}
+
 int comm_init(fmi_comm_t* comm, const void* id, int nranks, int rank, double timeout_s);
 
 int check_allreduce_args(int alg, int path) {
@@ -1970,6 +2021,23 @@ static int comm_allreduce_impl(fmi_comm_t comm, int op, int dtype, int alg, int 
     Comm* c = static_cast<Comm*>(comm);
     std::lock_guard<std::mutex> lk(c->mu);
     return allreduce_device(c, op, dtype, kd, alg, path, send, recv, n, resolve_stream(stream));
+}
+
+static int comm_allreduce_scaled_impl(fmi_comm_t comm, int op, int dtype_arg, int alg, int out_dtype, const void* send,
+                                      const float* in_scale, void* recv, const float* out_scale, float* amax, size_t n,
+                                      fmi_stream_t stream) {
+    int dtype = 0;
+    FMI_COMM_RC(scaled_check_args("fmi_comm_allreduce_scaled", op, dtype_arg, alg, out_dtype, &dtype));
+    if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE_LTR)
+        return fail(FMI_ERR_INVALID, "fmi_comm_allreduce_scaled: alg must be ALLREDUCE or REDUCE_LTR");
+    if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
+    if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
+    if (static_cast<Comm*>(comm)->t->aborted()) return aborted_error();
+    if (n == 0) return FMI_OK;
+    if (!send || !recv || !in_scale) return fail(FMI_ERR_INVALID, "null bucket");
+    Comm* c = static_cast<Comm*>(comm);
+    std::lock_guard<std::mutex> lk(c->mu);
+    return allreduce_scaled_device(c, dtype, alg, out_dtype, send, in_scale, recv, out_scale, amax, n, resolve_stream(stream));
 }
 
 // Three-stage pipeline over HostPipe::depth() chunk slots: while chunk k is allreduced on pipe.cs, chunk k+1 loads on
@@ -2268,6 +2336,14 @@ int fmi_comm_window_free(fmi_comm_t comm, void* ptr) {
 int fmi_comm_allreduce(fmi_comm_t comm, int op, int dtype, int alg, int path, const void* send, void* recv, size_t n,
                        fmi_stream_t stream) {
     return on_stream("fmi_comm_allreduce", comm, stream, [&] { return comm_allreduce_impl(comm, op, dtype, alg, path, send, recv, n, stream); });
+}
+
+int fmi_comm_allreduce_scaled(fmi_comm_t comm, int op, int dtype, int alg, int out_dtype, const void* send,
+                              const float* in_scale, void* recv, const float* out_scale, float* amax, size_t n,
+                              fmi_stream_t stream) {
+    return on_stream("fmi_comm_allreduce_scaled", comm, stream, [&] {
+        return comm_allreduce_scaled_impl(comm, op, dtype, alg, out_dtype, send, in_scale, recv, out_scale, amax, n, stream);
+    });
 }
 
 int fmi_comm_allreduce_host(fmi_comm_t comm, int op, int dtype, int alg, int path, const void* send, void* recv,

@@ -1752,3 +1752,85 @@ int fmi_tune_get(int key, long long* value) {
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------------------------
+// fmi_dev_reduce_tree_scaled (include/fmi_dev.h): the scaled sum of 8-bit float buckets.
+// ----------------------------------------------------------------------------------------------------
+namespace fmi::dev {
+
+// The host-side checks fmi_dev_reduce_tree_scaled and fmi_comm_allreduce_scaled share, before a device is needed.
+// *dtype: the storage dtype (FMI_ACC_F32 accepted and dropped: the call is f32-valued by definition).
+int scaled_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype, int* dtype) {
+    const std::string w = std::string(who) + ": ";
+    if (int rc = refuse_avg(op, who, "the call is a scaled sum; fold 1 / P into out_scale")) return rc;
+    if (op != FMI_OP_SUM)
+        return fail(FMI_ERR_INVALID, w + "op " + std::to_string(op) + " is not valid here: only FMI_OP_SUM is a scaled reduction "
+                                         "(PROD / MAX / MIN are out of scope)");
+    *dtype = storage_dtype(dtype_arg);
+    if (!is_fp8_dtype(*dtype))
+        return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype_arg) + " is not FMI_F8E4M3 or FMI_F8E5M2, the storage "
+                                         "types a scaled bucket can have");
+    if (alg == FMI_ALG_SCAN || alg == FMI_ALG_SCAN_LTR)
+        return fail(FMI_ERR_INVALID, w + "alg " + std::to_string(alg) + " is a scan algorithm; a scaled reduction takes "
+                                         "FMI_ALG_ALLREDUCE, FMI_ALG_REDUCE or FMI_ALG_REDUCE_LTR");
+    if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
+        return fail(FMI_ERR_INVALID, w + "unknown alg " + std::to_string(alg));
+    if (out_dtype != *dtype && out_dtype != FMI_F32)
+        return fail(FMI_ERR_INVALID, w + "out_dtype " + std::to_string(out_dtype) + " must be the input dtype (" +
+                                         std::to_string(*dtype) + ") or FMI_F32");
+    return FMI_OK;
+}
+
+int reduce_tree_scaled(int dtype, int alg, int out_dtype, void* out, const void* const* ins, const float* in_scales,
+                       const float* out_scale, float* amax, int P, int rank, size_t n, hipStream_t s) {
+    if (n == 0) return FMI_OK;
+    bool aligned = aligned16(out);
+    for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]);
+    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned) {
+        // reduce_no_order's transformed ids, as in fmi_dev_reduce_tree: slot t takes peer (t + root) % P, and the
+        // kernel reads that peer's scale (ScaledArgs::rot)
+        const int rot = alg == FMI_ALG_REDUCE ? rank : 0;
+        PeerPtrs ptrs{};
+        for (int t = 0; t < P; ++t) ptrs.in[t] = ins[(t + rot) % P];
+        ptrs.out[0] = out;
+        return launch_fused_scaled(alg, dtype, out_dtype, P, ptrs, ScaledArgs{in_scales, out_scale, amax, rot}, n, s);
+    }
+    // Beyond the fused kernels: v_p into f32 temporaries (FMI_ACC_F32's allocation and lock), the library's own FMI_F32
+    // SUM program on them (it applies the root's rotation itself) into a temporary of its own, the finishing kernel.
+    const size_t stride = arena_stride(n, sizeof(float));
+    size_t need = 0;
+    if (__builtin_mul_overflow(stride, static_cast<size_t>(P) + 1, &need))
+        return fail(FMI_ERR_ALLOC, "fmi_dev_reduce_tree_scaled's f32 temporaries: size overflows");
+    std::lock_guard<std::mutex> lk(g_acc_mu);
+    FMI_RC_TRY(acc_acquire(need, s));
+    auto temp = [&](int k) { return reinterpret_cast<float*>(static_cast<char*>(g_acc.buf) + stride * static_cast<size_t>(k)); };
+    std::vector<const void*> fin(P);
+    int rc = FMI_OK;
+    for (int p = 0; p < P && rc == FMI_OK; ++p) {
+        fin[p] = temp(p);
+        rc = launch_widen_scale_f32(dtype, temp(p), ins[p], in_scales + p, n, s);
+    }
+    // P = 1: S is v_0 itself (the f32 program would copy it)
+    if (rc == FMI_OK && P > 1) rc = reduce_tree_impl(FMI_OP_SUM, FMI_F32, alg, temp(P), fin.data(), P, rank, n, s);
+    if (rc == FMI_OK) rc = launch_scaled_finish(dtype, out_dtype, out, temp(P > 1 ? P : 0), out_scale, amax, n, s);
+    FMI_HIP_TRY(hipEventRecord(g_acc.free, s));
+    return rc;
+}
+
+}  // namespace fmi::dev
+
+int fmi_dev_reduce_tree_scaled(int op, int dtype_arg, int alg, int out_dtype, void* out, const void* const* ins,
+                               const float* in_scales, const float* out_scale, float* amax, int P, int rank, size_t n,
+                               fmi_stream_t stream) {
+    return guarded("fmi_dev_reduce_tree_scaled", [&]() -> int {
+        int dtype = 0;
+        if (int rc = scaled_check_args("fmi_dev_reduce_tree_scaled", op, dtype_arg, alg, out_dtype, &dtype)) return rc;
+        if (int rc = check_peer_args(op, dtype, P)) return rc;
+        if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
+        if (!out || !ins || !in_scales) return fail(FMI_ERR_INVALID, "null buffer");
+        for (int p = 0; p < P; ++p)
+            if (!ins[p]) return fail(FMI_ERR_INVALID, "null input bucket");
+        if (int rc = require_device()) return rc;
+        return reduce_tree_scaled(dtype, alg, out_dtype, out, ins, in_scales, out_scale, amax, P, rank, n, resolve(stream));
+    });
+}

@@ -10,6 +10,8 @@
 //   FMI_ACC_F32, 16-bit      fmi_fused_acc32_*.hip, one per algorithm
 //   FMI_ACC_F32, 8-bit       fmi_fused_fp8_acc32_*.hip, one per algorithm (sum, prod and the mean)
 //   FMI_OP_AVG               fmi_fused_avg_*.hip, one per reduce algorithm (f32 f64 f16 bf16, the last two with f32 values too)
+//   scaled 8-bit sums        fmi_fused_fp8_scaled_*.hip, one per reduce algorithm (fmi_dev_reduce_tree_scaled: both 8-bit
+//                            floats, 8-bit and f32 output; their own entry, launch_fused_scaled below)
 // Everything else a call can be runs elsewhere (fmi_dev.hip): P beyond a variant's kernels and unaligned buckets as
 // blocks of fused programs, as widen / the f32 program / narrow, as the SUM program and the scale kernel
 // (fmi_scale.hip), or as pairwise passes in the program's order.
@@ -118,6 +120,16 @@ int launch_fused(int alg, int op, int dtype_arg, int P, const PeerPtrs& ptrs, si
                                                                            : "no kernel for this algorithm and P";
     return fail(FMI_ERR_INVALID, "fused launch (algorithm " + std::to_string(alg) + ", op " + std::to_string(op) + ", dtype " +
                                      std::to_string(dtype_arg) + ", P = " + std::to_string(P) + "): " + why);
+}
+
+int launch_fused_scaled(int alg, int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const ScaledArgs& sc, size_t n, hipStream_t s) {
+    // a sum's bits are every rank's, so no allreduce call needs a permutation or a rank
+    switch (alg) {
+        case sched::kAllreduce: return scaled_unit<sched::kAllreduce>(dtype, out_dtype, P, ptrs, sc, n, s);
+        case sched::kReduce: return scaled_unit<sched::kReduce>(dtype, out_dtype, P, ptrs, sc, n, s);
+        case sched::kReduceLtr: return scaled_unit<sched::kReduceLtr>(dtype, out_dtype, P, ptrs, sc, n, s);
+        default: return fail(FMI_ERR_INVALID, "fused scaled launch: no kernel for algorithm " + std::to_string(alg));
+    }
 }
 
 int launch_fused_all_ranks(int op, int dtype, int P, const PeerPtrs& ptrs, size_t n, hipStream_t s) {

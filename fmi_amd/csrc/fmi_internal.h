@@ -208,6 +208,38 @@ inline constexpr int kRankEvery = 2;   // every rank's, out[r] for r < P: the sc
 using FusedUnit = int(int op, int dtype_arg, int P, const PeerPtrs& ptrs, size_t n, int rank, hipStream_t s);
 template <int ALG, int VAR, int LO, int HI, int RANKS = kRankZero>
 FusedUnit fused_unit;
+// fmi_dev_reduce_tree_scaled (include/fmi_dev.h): the scaled sum of 8-bit float buckets. What its kernels take beside
+// the peer pointers, every pointer device memory: in_scales[P] in the CALLER's peer order (the kernel reads input slot
+// t's scale at (t + rot) % P: rot = the root of a kReduce call, whose pointers the caller rotated, 0 otherwise),
+// out_scale and amax one f32 each, either may be nullptr.
+struct ScaledArgs {
+    const float* in_scales;
+    const float* out_scale;
+    float* amax;
+    int rot;
+};
+// The fused scaled kernels (fmi_fused.hip -> fmi_fused_fp8_scaled_*.hip): 2 <= P <= 16, all pointers 16-B aligned.
+// alg: kAllreduce, kReduce or kReduceLtr; dtype: FMI_F8E4M3 / FMI_F8E5M2; out_dtype: dtype or FMI_F32; ptrs.in[t] the
+// (transformed) inputs, ptrs.out[0] the result.
+int launch_fused_scaled(int alg, int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const ScaledArgs& sc, size_t n, hipStream_t s);
+// One translation unit's scaled kernels (algorithm ALG, P = 2..16, both dtypes, both outputs): declared here for the
+// dispatcher, defined in fmi_fp8_scaled_impl.h, instantiated by one fmi_fused_fp8_scaled_*.hip each.
+using ScaledUnit = int(int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const ScaledArgs& sc, size_t n, hipStream_t s);
+template <int ALG>
+ScaledUnit scaled_unit;
+// The scaled call's other kernels (fmi_fp8_scaled.hip), any alignment. dtype / out_dtype as above.
+//   widen_scale: dst[i] = fl32(widen(src[i]) * *scale)
+//   finish:      amax (if given) folded with max bits(|S[i]|); out[i] = narrow(fl32(S[i] * t)) or fl32(S[i] * t)
+//   amax_fold:   *amax = umax(bits(*amax), words[0..count))
+int launch_widen_scale_f32(int dtype, float* dst, const void* src, const float* scale, size_t n, hipStream_t s);
+int launch_scaled_finish(int dtype, int out_dtype, void* out, const float* S, const float* out_scale, float* amax, size_t n,
+                         hipStream_t s);
+int launch_amax_fold(float* amax, const uint32_t* words, int count, hipStream_t s);
+// The host-side checks of fmi_dev_reduce_tree_scaled's op, dtype argument, alg and out_dtype (fmi_dev.hip), shared with
+// fmi_comm_allreduce_scaled; *dtype: the storage dtype. And the call after its validation: the comm call's shard step.
+int scaled_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype, int* dtype);
+int reduce_tree_scaled(int dtype, int alg, int out_dtype, void* out, const void* const* ins, const float* in_scales,
+                       const float* out_scale, float* amax, int P, int rank, size_t n, hipStream_t s);
 // kReducePartials for any P and any alignment / dtype (fused kernel where it applies, pairwise passes otherwise):
 // outs[t] = the value transformed peer t of reduce_no_order holds in its sendbuf at the end
 // (src/comm/PeerToPeer.cpp:66-78); ins in transformed order. Defined in fmi_dev.hip.

@@ -387,6 +387,34 @@ def reduce_tree(op: Op, alg: Alg, out: Bucket, ins: Sequence[Bucket], rank: int 
               out.n, _sptr(stream))
 
 
+def _f32_word(b, what: str, n: int = 1) -> Optional[int]:
+    if b is None:
+        return None
+    if not isinstance(b, Bucket) or b.dtype != DType.F32 or b.n < n:
+        raise ValueError(f"{what} must be an F32 bucket of at least {n} element(s)")
+    return b.ptr
+
+
+def reduce_tree_scaled(alg: Alg, out: Bucket, ins: Sequence[Bucket], in_scales: Bucket, out_scale: Optional[Bucket] = None,
+                       amax: Optional[Bucket] = None, rank: int = 0, stream=None) -> None:
+    """The scaled sum of F8E4M3 / F8E5M2 buckets (fmi_dev_reduce_tree_scaled): every input times its own scale in f32,
+    the f32 SUM program of `alg`, amax of the sum folded into `amax`, the sum times `out_scale`, stored once into `out`:
+    a bucket of the inputs' dtype (non-saturating narrowing) or an F32 bucket. in_scales (one per peer), out_scale and
+    amax are F32 buckets: the scales live on the device, so a captured graph replays with new ones. One fused kernel at
+    2..16 peers on 16-B aligned buckets."""
+    if not ins:
+        raise ValueError("need at least one peer bucket")
+    dtype = ins[0].dtype
+    if dtype not in (DType.F8E4M3, DType.F8E5M2):
+        raise ValueError(f"reduce_tree_scaled needs F8E4M3 or F8E5M2 input buckets, got {DType(dtype).name}")
+    _check_peers(ins[0], ins)
+    if out.n != ins[0].n or out.dtype not in (dtype, DType.F32):
+        raise ValueError("reduce_tree_scaled: `out` must hold the inputs' length in their dtype or in F32")
+    _lib.call("fmi_dev_reduce_tree_scaled", int(Op.SUM), int(dtype), int(alg), int(out.dtype), out.ptr, _ptr_array(ins),
+              _f32_word(in_scales, "in_scales", len(ins)), _f32_word(out_scale, "out_scale"), _f32_word(amax, "amax"),
+              len(ins), rank, out.n, _sptr(stream))
+
+
 def mean_scale(inout: Bucket, P: int, n: Optional[int] = None, stream=None) -> None:
     """inout = inout * fl(1 / P) in place (fmi_dev_mean_scale): Op.AVG's last step alone, for a SUM that went through
     an exchange of the caller's own. Float buckets; f16 / bf16 multiply in f32 and round to storage once."""

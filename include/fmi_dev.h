@@ -335,6 +335,34 @@ int fmi_dev_mean_scale(int dtype, void* inout, size_t n, int P, fmi_stream_t str
  * It is FMI_ACC_F32's fallback conversion made public: how f32 / bf16 data gets into an 8-bit float bucket. */
 int fmi_dev_convert(int dst_dtype, void* dst, int src_dtype, const void* src, size_t n, fmi_stream_t stream);
 
+/* Scaled P-way sum of 8-bit float buckets: what an FP8 gradient bucket with per-producer scales needs, in one pass.
+ * dtype: FMI_F8E4M3 or FMI_F8E5M2, the storage type of every ins[p] (FMI_ACC_F32 is accepted and dropped: the call is
+ * f32-valued by definition). in_scales: P f32 values in DEVICE memory, in_scales[p] the scale of ins[p]; out_scale
+ * (NULL = 1.0f) and amax (NULL = not wanted): one f32 each in device memory. They live on the device so that a captured
+ * graph picks up new scales on replay and delayed-scaling code never synchronises. Per element, with s_p = in_scales[p]
+ * and t = *out_scale:
+ *     v_p  = fl32( widen(x_p) * s_p )                  one IEEE f32 multiply per input
+ *     S    = F32_program_alg( v_0 .. v_{P-1} )         the FMI_F32 SUM program of `alg`, the same bracketing
+ *     amax = umax over the elements of bits(|S|), folded into what *amax held
+ *     out  = narrow_dtype( fl32( S * t ) )             if out_dtype == dtype (the non-saturating narrowing above)
+ *     out  =               fl32( S * t )               if out_dtype == FMI_F32
+ * Every operation is round-to-nearest-even with subnormals kept and no contraction: the multiply by s_p is not fused
+ * into the add that follows it, the multiply by t not into the narrowing. amax is of S, BEFORE the output scale (the
+ * convention of delayed scaling), and is defined on the bit patterns of |S| compared as unsigned integers: it does not
+ * depend on any order (deterministic), and a NaN in S wins and gives some NaN. *amax is read-modify-written: the caller
+ * zeroes it and may accumulate over several buckets; it must hold a non-negative float or a NaN on entry.
+ * Valid: op FMI_OP_SUM only (FMI_OP_AVG: FMI_ERR_INVALID, fold 1/P into out_scale; PROD / MAX / MIN: FMI_ERR_INVALID);
+ * alg FMI_ALG_ALLREDUCE, _REDUCE or _REDUCE_LTR with `rank` as in fmi_dev_reduce_tree; out_dtype == dtype or FMI_F32;
+ * P >= 1, and P = 1 is NOT a copy: out = narrow(fl32(fl32(widen(x) * s_0) * t)). All of it is checked on the host before
+ * a device is needed. out may alias an ins[p] only where out_dtype == dtype.
+ * 2 <= P <= 16 with every bucket 16-B aligned: ONE fused kernel (P reads, one store, at most one atomic per
+ * workgroup), graph-capturable. Any other call (P = 1, P > 16, unaligned buckets) widens and scales every input into an
+ * f32 temporary (FMI_ACC_F32's allocation: not capturable), runs the library's own FMI_F32 program on those and one
+ * finishing kernel (amax, x t, narrow or store): the same bits by construction. Additive: fmi_abi_version() stays 1. */
+int fmi_dev_reduce_tree_scaled(int op, int dtype, int alg, int out_dtype, void* out, const void* const* ins,
+                               const float* in_scales, const float* out_scale, float* amax, int P, int rank, size_t n,
+                               fmi_stream_t stream);
+
 /* Peer-axis inclusive scan of P device buckets: outs[k] = x0 (+) ... (+) xk with the evaluation order
  * of `alg` (FMI_ALG_SCAN or FMI_ALG_SCAN_LTR). Replaces reference PeerToPeer::scan_no_order / scan_ltr
  * (src/comm/PeerToPeer.cpp:154-184, :141-152) and Communicator::scan (include/Communicator.h:135-150)
@@ -435,6 +463,18 @@ int fmi_comm_timing_read(fmi_comm_t comm, float* total_ms, int* launches);
 /* alg: FMI_ALG_ALLREDUCE (commutative+associative) or FMI_ALG_REDUCE_LTR (ordered) */
 int fmi_comm_allreduce(fmi_comm_t comm, int op, int dtype, int alg, int path, const void* send, void* recv, size_t n,
                        fmi_stream_t stream);
+/* The sharded allreduce of scaled 8-bit float buckets (fmi_dev_reduce_tree_scaled above): path TREE, unpipelined, on
+ * every transport. op: FMI_OP_SUM; dtype, out_dtype as there; alg: FMI_ALG_ALLREDUCE or FMI_ALG_REDUCE_LTR. `send` holds
+ * n elements of dtype, `recv` n of out_dtype; in_scale is this rank's ONE scale, out_scale (NULL = 1.0f) and amax (NULL =
+ * not wanted) one f32 each, all in device memory. The input shards travel as 8-bit bytes; the N scales are all-gathered
+ * (4 bytes per rank) into rank order; each owner runs fmi_dev_reduce_tree_scaled at P = N, rank 0, on its shard's true
+ * length (no padding reaches amax); the result shards are all-gathered at out_dtype's element size; the owners' shard
+ * amax words are all-gathered and folded, with what *amax held, into *amax: every rank ends with the same amax. Every
+ * rank's recv is the program of `alg` over v_p in rank order. out_scale must hold the same value on every rank. `send`
+ * is not modified. A one-rank communicator runs the P = 1 form. */
+int fmi_comm_allreduce_scaled(fmi_comm_t comm, int op, int dtype, int alg, int out_dtype, const void* send,
+                              const float* in_scale, void* recv, const float* out_scale, float* amax, size_t n,
+                              fmi_stream_t stream);
 /* Host-ingress allreduce (BASELINE config C5): `send` / `recv` are HOST buckets, i.e. the channel recv
  * buffers FMI's transports deliver into (reference src/comm/Direct.cpp:36-45, PeerToPeer.cpp:110-129).
  * The bucket streams through the GPU in chunks of `chunk` elements (0 = FMI_TUNE_HOST_CHUNK bytes):
