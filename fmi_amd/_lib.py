@@ -98,6 +98,9 @@ SIGNATURES = {
     "fmi_dev_mean_scale": (_i, [_i, _vp, _sz, _i, _vp]),
     "fmi_dev_convert": (_i, [_i, _vp, _i, _vp, _sz, _vp]),
     "fmi_dev_reduce_tree_scaled": (_i, [_i, _i, _i, _i, _vp, _c.POINTER(_vp), _vp, _vp, _vp, _i, _i, _sz, _vp]),
+    "fmi_dev_reduce_tree_mx": (_i, [_i, _i, _i, _i, _vp, _vp, _c.POINTER(_vp), _c.POINTER(_vp), _i, _i, _sz, _vp]),
+    "fmi_dev_mx_quantize": (_i, [_i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "fmi_dev_mx_dequantize": (_i, [_i, _vp, _i, _vp, _vp, _sz, _vp]),
     "fmi_host_reduce_pair": (_i, [_i, _i, _vp, _vp, _sz]),
     "fmi_host_device_ptr": (_i, [_vp, _sz, _c.POINTER(_vp)]),
     "fmi_host_page_locked": (_i, [_vp, _sz]),
@@ -115,6 +118,7 @@ SIGNATURES = {
     "fmi_comm_timing_read": (_i, [_vp, _c.POINTER(_c.c_float), _c.POINTER(_i)]),
     "fmi_comm_allreduce": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "fmi_comm_allreduce_scaled": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "fmi_comm_allreduce_mx": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fmi_comm_allreduce_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _sz]),
     "fmi_comm_reduce": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _i, _vp]),
     "fmi_comm_reduce_sendbuf": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _i, _vp]),

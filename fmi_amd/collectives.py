@@ -102,6 +102,37 @@ class HipEngine:
                   in_scales.data_ptr(), out_scale.data_ptr() if out_scale is not None else None,
                   amax.data_ptr() if amax is not None else None, len(ins), rank, out.numel(), self._stream())
 
+    def reduce_tree_mx(self, op: Op, alg: Alg, out: torch.Tensor, out_scales: Optional[torch.Tensor],
+                       ins: Sequence[torch.Tensor], in_scales: Sequence[torch.Tensor], rank: int = 0) -> None:
+        """The sum or mean of block-scaled (MX) float8 tensors (fmi_dev_reduce_tree_mx): `ins` are float8_e4m3fn /
+        float8_e5m2 tensors, `in_scales` their float8_e8m0fnu (or uint8) scale tensors of ceil(n / 32) elements; `out` is
+        a tensor of the inputs' dtype with `out_scales`, or of float32 with out_scales None."""
+        import ctypes
+        dtype = _dtype(ins[0])
+        if dtype not in (DType.F8E4M3, DType.F8E5M2):
+            raise TypeError(f"reduce_tree_mx needs float8_e4m3fn or float8_e5m2 inputs, got {ins[0].dtype}")
+        if any(t.dtype != ins[0].dtype or t.numel() != out.numel() or not t.is_contiguous() for t in ins):
+            raise ValueError("reduce_tree_mx: contiguous inputs of one dtype and of out's length")
+        if out.dtype not in (ins[0].dtype, torch.float32) or not out.is_contiguous():
+            raise ValueError("reduce_tree_mx: `out` is a contiguous tensor of the inputs' dtype or of float32")
+        if len(in_scales) != len(ins):
+            raise ValueError("reduce_tree_mx: one in_scales tensor per input")
+        if out.dtype != torch.float32 and out_scales is None:
+            raise ValueError("reduce_tree_mx: out_scales is missing: only a float32 output has no scale bytes")
+        scale_types = tuple(getattr(torch, k) for k in ("float8_e8m0fnu", "uint8") if hasattr(torch, k))
+        blocks = (out.numel() + 31) // 32
+        named = [(f"in_scales[{p}]", t) for p, t in enumerate(in_scales)] + ([("out_scales", out_scales)] if out_scales is not None else [])
+        for name, t in named:
+            if t.dtype not in scale_types or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"reduce_tree_mx: {name} must be a contiguous float8_e8m0fnu (or uint8) device tensor")
+            if t.numel() != blocks:
+                raise ValueError(f"reduce_tree_mx: {name} must hold ceil(n / 32) = {blocks} scale bytes, got {t.numel()}")
+        ptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
+        sptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in in_scales])
+        _lib.call("fmi_dev_reduce_tree_mx", int(op), int(dtype), int(alg), int(_dtype(out)), out.data_ptr(),
+                  out_scales.data_ptr() if out_scales is not None else None, ptrs, sptrs, len(ins), rank, out.numel(),
+                  self._stream())
+
     def fill_synthetic(self, t: torch.Tensor, seed: int, peer: int) -> None:
         _lib.call("fmi_dev_fill_synthetic", int(_dtype(t)), t.data_ptr(), t.numel(), seed, peer, self._stream())
 

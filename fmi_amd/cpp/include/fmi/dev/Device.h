@@ -195,6 +195,27 @@ static_assert(sizeof(float8_e4m3) == 1 && sizeof(float8_e5m2) == 1 && std::is_tr
                   std::is_trivially_copyable_v<float8_e5m2>,
               "8-bit float elements are their raw bits");
 
+// The scale byte of an MX bucket (OCP E8M0): 2^(bits - 127) for 1..254, 2^-127 for 0, NaN for 255; one per 32 elements
+// (reduce_tree_mx below). A byte type with a value, no arithmetic, and a label only: it has no C-ABI dtype, so dtype_of
+// answers -1 and no reduction, conversion or fill takes a bucket of it; Bucket stores it (bucket_storage below).
+struct float8_e8m0 {
+    std::uint8_t bits = 127;  // 1.0
+    float8_e8m0() = default;
+    static float8_e8m0 from_bits(std::uint8_t b) {
+        float8_e8m0 x;
+        x.bits = b;
+        return x;
+    }
+    explicit operator float() const {
+        const std::uint32_t u = bits == 0 ? 0x00400000u : bits == 255 ? 0x7FC00000u : static_cast<std::uint32_t>(bits) << 23;
+        float f;
+        std::memcpy(&f, &u, sizeof f);
+        return f;
+    }
+};
+inline bool operator==(float8_e8m0 a, float8_e8m0 b) { return a.bits == b.bits; }
+static_assert(sizeof(float8_e8m0) == 1 && std::is_trivially_copyable_v<float8_e8m0>, "a scale is its raw byte");
+
 // The float element types narrower than float: their values are held and scaled (the mean) in float.
 template <class A>
 inline constexpr bool narrow_float_v = std::is_same_v<A, half> || std::is_same_v<A, bfloat16> ||
@@ -227,6 +248,9 @@ constexpr int dtype_of() {
 
 template <class A>
 constexpr bool device_type = dtype_of<A>() >= 0;
+// What a Bucket can hold: the device element types, and the scale bytes of MX buckets, which only the MX calls take.
+template <class A>
+constexpr bool bucket_storage = device_type<A> || std::is_same_v<A, float8_e8m0>;
 
 // Select the device for this process (one process per GPU, as FMI runs one peer per process).
 inline void init(int device = 0) { check(fmi_dev_init(device), "fmi_dev_init"); }
@@ -241,7 +265,7 @@ inline void sync() { check(fmi_dev_sync(), "fmi_dev_sync"); }
 // A device-resident bucket of n elements of A (owning, move-only).
 template <class A>
 class Bucket {
-    static_assert(device_type<A>, "device buckets hold float, double, Dev::half, Dev::bfloat16, Dev::float8_e4m3, Dev::float8_e5m2 or 8/16/32/64-bit integers");
+    static_assert(bucket_storage<A>, "device buckets hold float, double, Dev::half, Dev::bfloat16, Dev::float8_e4m3, Dev::float8_e5m2, 8/16/32/64-bit integers or Dev::float8_e8m0 scale bytes");
 
 public:
     using value_type = A;
@@ -305,6 +329,7 @@ public:
         return host;
     }
     void fill_synthetic(uint64_t seed, uint32_t peer) {
+        static_assert(device_type<A>, "fill_synthetic: a device element type (scale bytes have no synthetic fill)");
         check(fmi_dev_fill_synthetic(dtype_of<A>(), ptr_, n_, seed, peer, nullptr), "fmi_dev_fill_synthetic");
     }
 
@@ -355,6 +380,65 @@ inline void reduce_tree_scaled(int alg, Bucket<O>& out, const std::vector<const 
                                      out_scale ? out_scale->data() : nullptr, amax ? amax->data() : nullptr,
                                      static_cast<int>(ins.size()), rank, out.size(), stream),
           "fmi_dev_reduce_tree_scaled");
+}
+
+// Block-scaled (MX) 8-bit float buckets (fmi_dev_reduce_tree_mx): n elements of Dev::float8_e4m3 / Dev::float8_e5m2 and
+// (n + 31) / 32 Dev::float8_e8m0 scale bytes, one per 32 elements.
+inline std::size_t mx_blocks(std::size_t n) { return (n + 31) / 32; }
+
+// The sum (FMI_OP_SUM) or mean (FMI_OP_AVG) of MX buckets: every element times its block's scale in float, the float SUM
+// program of `alg` (`rank` as in fmi_dev_reduce_tree), then per block of 32 the smallest power-of-two scale that brings
+// the block's largest magnitude within the element type, into out_scales, and the scaled sum narrowed into `out`; or,
+// into a Bucket<float>, the sum itself and no output scales.
+namespace detail {
+template <class A>
+inline void reduce_tree_mx(int op, int alg, int out_dtype, void* out, void* out_scales, std::size_t n,
+                           const std::vector<const Bucket<A>*>& ins, const std::vector<const Bucket<float8_e8m0>*>& in_scales,
+                           int rank, fmi_stream_t stream) {
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>,
+                  "reduce_tree_mx: Dev::float8_e4m3 or Dev::float8_e5m2 elements");
+    if (ins.empty() || ins.size() > static_cast<std::size_t>(std::numeric_limits<int>::max()) || in_scales.size() != ins.size())
+        throw std::runtime_error("Dev::reduce_tree_mx: need at least one input bucket and one scale bucket per input");
+    std::vector<const void*> ptrs, sptrs;
+    for (std::size_t p = 0; p < ins.size(); ++p) {
+        if (!ins[p] || ins[p]->size() != n) throw std::runtime_error("Dev::reduce_tree_mx: size mismatch");
+        if (!in_scales[p] || in_scales[p]->size() != mx_blocks(n))
+            throw std::runtime_error("Dev::reduce_tree_mx: a scale bucket holds (n + 31) / 32 bytes");
+        ptrs.push_back(ins[p]->data());
+        sptrs.push_back(in_scales[p]->data());
+    }
+    check(fmi_dev_reduce_tree_mx(op, dtype_of<A>(), alg, out_dtype, out, out_scales, ptrs.data(), sptrs.data(),
+                                 static_cast<int>(ins.size()), rank, n, stream),
+          "fmi_dev_reduce_tree_mx");
+}
+}  // namespace detail
+
+template <class A>
+inline void reduce_tree_mx(int op, int alg, Bucket<A>& out, Bucket<float8_e8m0>& out_scales, const std::vector<const Bucket<A>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank = 0, fmi_stream_t stream = nullptr) {
+    if (out_scales.size() != mx_blocks(out.size())) throw std::runtime_error("Dev::reduce_tree_mx: out_scales holds (n + 31) / 32 bytes");
+    detail::reduce_tree_mx(op, alg, dtype_of<A>(), out.data(), out_scales.data(), out.size(), ins, in_scales, rank, stream);
+}
+template <class A>
+inline void reduce_tree_mx(int op, int alg, Bucket<float>& out, const std::vector<const Bucket<A>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank = 0, fmi_stream_t stream = nullptr) {
+    detail::reduce_tree_mx(op, alg, FMI_F32, out.data(), nullptr, out.size(), ins, in_scales, rank, stream);
+}
+
+// float / Dev::half / Dev::bfloat16 data into an MX bucket and back (fmi_dev_mx_quantize / fmi_dev_mx_dequantize).
+template <class A, class S>
+inline void mx_quantize(Bucket<A>& out, Bucket<float8_e8m0>& out_scales, const Bucket<S>& src, fmi_stream_t stream = nullptr) {
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>, "mx_quantize: Dev::float8_e4m3 or Dev::float8_e5m2 elements");
+    static_assert(std::is_same_v<S, float> || std::is_same_v<S, half> || std::is_same_v<S, bfloat16>, "mx_quantize: float, Dev::half or Dev::bfloat16 source");
+    if (out.size() != src.size() || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
+    check(fmi_dev_mx_quantize(dtype_of<A>(), out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), stream), "fmi_dev_mx_quantize");
+}
+template <class D, class A>
+inline void mx_dequantize(Bucket<D>& dst, const Bucket<A>& src, const Bucket<float8_e8m0>& src_scales, fmi_stream_t stream = nullptr) {
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>, "mx_dequantize: Dev::float8_e4m3 or Dev::float8_e5m2 elements");
+    static_assert(std::is_same_v<D, float> || std::is_same_v<D, half> || std::is_same_v<D, bfloat16>, "mx_dequantize: float, Dev::half or Dev::bfloat16 destination");
+    if (dst.size() != src.size() || src_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_dequantize: size mismatch");
+    check(fmi_dev_mx_dequantize(dtype_of<D>(), dst.data(), dtype_of<A>(), src.data(), src_scales.data(), src.size(), stream), "fmi_dev_mx_dequantize");
 }
 
 // Untyped device scratch used by the channel algorithms for temporaries of device-resident buckets.

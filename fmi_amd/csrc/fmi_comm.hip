@@ -1302,8 +1302,9 @@ struct KernelTiming {
 
 struct Comm {
     // 0-3: collective scratch; 4-7 and 16-17: host-pipeline chunk slots (in / out x HostPipe::kDepth);
-    // 8-15: pipelined-allreduce slots (2 x 4); 18: the scaled allreduce's words (N scales, N amax words, this rank's)
-    static constexpr int kSlots = 19;
+    // 8-15: pipelined-allreduce slots (2 x 4); 18: the scaled allreduce's words (N scales, N amax words, this rank's);
+    // 19-22: the MX allreduce's scale bytes (padded source, staging, reduced shard, gathered)
+    static constexpr int kSlots = 23;
     std::unique_ptr<Transport> t;
     std::mutex mu;
     KernelTiming timing;
@@ -1782,6 +1783,64 @@ int allreduce_scaled_device(Comm* c, int dtype, int alg, int out_dtype, const vo
     return FMI_OK;
 }
 
+// fmi_comm_allreduce_mx (include/fmi_dev.h): allreduce_scaled_device over MX buckets. The scale bytes take the
+// elements' route on a grid of their own, shard / 32 bytes per shard (kShardAlign is 64 elements: every shard boundary
+// is a block boundary). The shard kernel runs on the shard's TRUE length, so a padded block is never computed.
+int allreduce_mx_device(Comm* c, int op, int dtype, int alg, int out_dtype, const void* send, const void* send_scales,
+                        void* recv, void* recv_scales, size_t n, hipStream_t s) {
+    const int N = c->t->n();
+    if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE))  // the P = 1 form: not a copy
+        return reduce_tree_mx(op, dtype, alg, out_dtype, recv, recv_scales, &send, &send_scales, 1, 0, n, s);
+    static_assert(kShardAlign % 32 == 0, "shard boundaries are MX block boundaries");
+    const bool wide = out_dtype == FMI_F32;
+    const size_t osz = dtype_size(out_dtype);  // the inputs' element size is 1
+    const size_t shard = shard_elems(n, N), padded = shard * N;
+    const size_t nsc = (n + 31) / 32, sshard = shard / 32, spadded = sshard * N;
+    const char* src = nullptr;
+    FMI_COMM_RC(padded_source(c, n, padded, 1, send, s, &src));
+    const char* ssrc = static_cast<const char*>(send_scales);
+    if (spadded != nsc) {
+        char* pad = nullptr;
+        FMI_COMM_RC(c->scratch(19, spadded, s, &pad));
+        FMI_COMM_HIP(hipMemcpyAsync(pad, send_scales, nsc, hipMemcpyDeviceToDevice, s));
+        FMI_COMM_HIP(hipMemsetAsync(pad + nsc, 0, spadded - nsc, s));
+        ssrc = pad;
+    }
+    char *staging = nullptr, *red = nullptr, *sstaging = nullptr, *sred = nullptr;
+    FMI_COMM_RC(c->scratch(1, padded, s, &staging));
+    FMI_COMM_RC(c->scratch(2, shard * osz, s, &red));
+    FMI_COMM_RC(c->scratch(20, spadded, s, &sstaging));
+    FMI_COMM_RC(c->scratch(21, sshard, s, &sred));
+    FMI_COMM_RC(c->t->all_to_all(src, staging, shard, s));
+    FMI_COMM_RC(c->t->all_to_all(ssrc, sstaging, sshard, s));
+    const size_t len = Transport::span(c->t->rank(), shard, n);  // elements of my shard
+    if (len) {
+        std::vector<const void*> parts(N), sparts(N);
+        for (int j = 0; j < N; ++j) parts[j] = staging + j * shard, sparts[j] = sstaging + j * sshard;
+        FMI_COMM_RC(c->timing.begin(s));
+        FMI_COMM_RC(reduce_tree_mx(op, dtype, alg, out_dtype, red, sred, parts.data(), sparts.data(), N, 0, len, s));
+        FMI_COMM_RC(c->timing.end(s));
+    }
+    if (padded == n) {
+        FMI_COMM_RC(c->t->all_gather(red, static_cast<char*>(recv), shard * osz, s));
+    } else {
+        char* out = nullptr;
+        FMI_COMM_RC(c->scratch(3, padded * osz, s, &out));
+        FMI_COMM_RC(c->t->all_gather(red, out, shard * osz, s));
+        FMI_COMM_RC(device_copy(recv, out, n * osz, s));
+    }
+    if (wide) return FMI_OK;
+    if (spadded == nsc) {
+        FMI_COMM_RC(c->t->all_gather(sred, static_cast<char*>(recv_scales), sshard, s));
+    } else {
+        char* out = nullptr;
+        FMI_COMM_RC(c->scratch(22, spadded, s, &out));
+        FMI_COMM_RC(c->t->all_gather(sred, out, sshard, s));
+        FMI_COMM_HIP(hipMemcpyAsync(recv_scales, out, nsc, hipMemcpyDeviceToDevice, s));
+    }
+    return FMI_OK;
+}
+
 int comm_init(fmi_comm_t* comm, const void* id, int nranks, int rank, double timeout_s);
 
 int check_allreduce_args(int alg, int path) {
@@ -2038,6 +2097,22 @@ static int comm_allreduce_scaled_impl(fmi_comm_t comm, int op, int dtype_arg, in
     Comm* c = static_cast<Comm*>(comm);
     std::lock_guard<std::mutex> lk(c->mu);
     return allreduce_scaled_device(c, dtype, alg, out_dtype, send, in_scale, recv, out_scale, amax, n, resolve_stream(stream));
+}
+
+static int comm_allreduce_mx_impl(fmi_comm_t comm, int op, int dtype_arg, int alg, int out_dtype, const void* send,
+                                  const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream) {
+    int dtype = 0;
+    FMI_COMM_RC(mx_check_args("fmi_comm_allreduce_mx", op, dtype_arg, alg, out_dtype, recv_scales, &dtype));
+    if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE_LTR)
+        return fail(FMI_ERR_INVALID, "fmi_comm_allreduce_mx: alg must be ALLREDUCE or REDUCE_LTR");
+    if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
+    if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
+    if (static_cast<Comm*>(comm)->t->aborted()) return aborted_error();
+    if (n == 0) return FMI_OK;
+    if (!send || !recv || !send_scales) return fail(FMI_ERR_INVALID, "null bucket");
+    Comm* c = static_cast<Comm*>(comm);
+    std::lock_guard<std::mutex> lk(c->mu);
+    return allreduce_mx_device(c, op, dtype, alg, out_dtype, send, send_scales, recv, recv_scales, n, resolve_stream(stream));
 }
 
 // Three-stage pipeline over HostPipe::depth() chunk slots: while chunk k is allreduced on pipe.cs, chunk k+1 loads on
@@ -2343,6 +2418,13 @@ int fmi_comm_allreduce_scaled(fmi_comm_t comm, int op, int dtype, int alg, int o
                               fmi_stream_t stream) {
     return on_stream("fmi_comm_allreduce_scaled", comm, stream, [&] {
         return comm_allreduce_scaled_impl(comm, op, dtype, alg, out_dtype, send, in_scale, recv, out_scale, amax, n, stream);
+    });
+}
+
+int fmi_comm_allreduce_mx(fmi_comm_t comm, int op, int dtype, int alg, int out_dtype, const void* send,
+                          const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream) {
+    return on_stream("fmi_comm_allreduce_mx", comm, stream, [&] {
+        return comm_allreduce_mx_impl(comm, op, dtype, alg, out_dtype, send, send_scales, recv, recv_scales, n, stream);
     });
 }
 

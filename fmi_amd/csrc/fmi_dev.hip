@@ -1834,3 +1834,130 @@ int fmi_dev_reduce_tree_scaled(int op, int dtype_arg, int alg, int out_dtype, vo
         return reduce_tree_scaled(dtype, alg, out_dtype, out, ins, in_scales, out_scale, amax, P, rank, n, resolve(stream));
     });
 }
+
+// ----------------------------------------------------------------------------------------------------
+// fmi_dev_reduce_tree_mx, fmi_dev_mx_quantize, fmi_dev_mx_dequantize (include/fmi_dev.h): block-scaled (MX) 8-bit
+// float buckets, one E8M0 scale byte per 32 elements.
+// ----------------------------------------------------------------------------------------------------
+namespace fmi::dev {
+
+// The host-side checks fmi_dev_reduce_tree_mx and fmi_comm_allreduce_mx share, before a device is needed.
+// *dtype: the storage dtype (FMI_ACC_F32 accepted and dropped: the call is f32-valued by definition).
+int mx_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype, const void* out_scales, int* dtype) {
+    const std::string w = std::string(who) + ": ";
+    if (op != FMI_OP_SUM && op != FMI_OP_AVG)
+        return fail(FMI_ERR_INVALID, w + "op " + std::to_string(op) + " is not valid here: an MX reduction is FMI_OP_SUM or "
+                                         "FMI_OP_AVG (PROD / MAX / MIN are out of scope)");
+    *dtype = storage_dtype(dtype_arg);
+    if (!is_fp8_dtype(*dtype))
+        return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype_arg) + " is not FMI_F8E4M3 or FMI_F8E5M2, the element "
+                                         "types an MX bucket can have");
+    if (alg == FMI_ALG_SCAN || alg == FMI_ALG_SCAN_LTR)
+        return fail(FMI_ERR_INVALID, w + "alg " + std::to_string(alg) + " is a scan algorithm; an MX reduction takes "
+                                         "FMI_ALG_ALLREDUCE, FMI_ALG_REDUCE or FMI_ALG_REDUCE_LTR");
+    if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
+        return fail(FMI_ERR_INVALID, w + "unknown alg " + std::to_string(alg));
+    if (out_dtype != *dtype && out_dtype != FMI_F32)
+        return fail(FMI_ERR_INVALID, w + "out_dtype " + std::to_string(out_dtype) + " must be the input dtype (" +
+                                         std::to_string(*dtype) + ") or FMI_F32");
+    if (out_dtype != FMI_F32 && !out_scales)
+        return fail(FMI_ERR_INVALID, w + "out_scales is NULL: an output of dtype " + std::to_string(out_dtype) +
+                                         " needs its scale bytes (only an FMI_F32 output has none)");
+    return FMI_OK;
+}
+
+// dtype: FMI_F8E4M3 / FMI_F8E5M2; wide: the other side's dtype, named `what` in the message.
+static int mx_check_convert(const char* who, int dtype, const char* what, int wide) {
+    const std::string w = std::string(who) + ": ";
+    if (!is_fp8_dtype(dtype))
+        return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype) + " is not FMI_F8E4M3 or FMI_F8E5M2, the element "
+                                         "types an MX bucket can have");
+    if (wide != FMI_F32 && wide != FMI_F16 && wide != FMI_BF16)
+        return fail(FMI_ERR_INVALID, w + what + " " + std::to_string(wide) + " must be FMI_F32, FMI_F16 or FMI_BF16");
+    return FMI_OK;
+}
+
+int reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* out_scales, const void* const* ins,
+                   const void* const* in_scales, int P, int rank, size_t n, hipStream_t s) {
+    if (n == 0) return FMI_OK;
+    const bool wide = out_dtype == FMI_F32;
+    bool aligned = aligned16(out);
+    for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]);
+    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned) {
+        // reduce_no_order's transformed ids, as in fmi_dev_reduce_tree: slot t takes peer (t + root) % P, its element
+        // bucket and its scale bytes alike
+        const int rot = alg == FMI_ALG_REDUCE ? rank : 0;
+        PeerPtrs ptrs{};
+        MxArgs mx{};
+        for (int t = 0; t < P; ++t) {
+            ptrs.in[t] = ins[(t + rot) % P];
+            mx.in_scales[t] = static_cast<const uint8_t*>(in_scales[(t + rot) % P]);
+        }
+        ptrs.out[0] = out;
+        mx.out_scales = static_cast<uint8_t*>(out_scales);
+        mx.r = op == FMI_OP_AVG ? 1.0f / static_cast<float>(P) : 1.0f;
+        return launch_fused_mx(alg, dtype, out_dtype, P, ptrs, mx, n, s);
+    }
+    // Beyond the fused kernels: v_p into f32 temporaries (FMI_ACC_F32's allocation and lock), the library's own FMI_F32
+    // program on them (sum or mean; it applies the root's rotation itself), then the quantize kernel. An f32 output
+    // takes the program's result directly.
+    const size_t stride = arena_stride(n, sizeof(float));
+    size_t need = 0;
+    if (__builtin_mul_overflow(stride, static_cast<size_t>(P) + 1, &need))
+        return fail(FMI_ERR_ALLOC, "fmi_dev_reduce_tree_mx's f32 temporaries: size overflows");
+    std::lock_guard<std::mutex> lk(g_acc_mu);
+    FMI_RC_TRY(acc_acquire(need, s));
+    auto temp = [&](int k) { return reinterpret_cast<float*>(static_cast<char*>(g_acc.buf) + stride * static_cast<size_t>(k)); };
+    std::vector<const void*> fin(P);
+    int rc = FMI_OK;
+    // P = 1: S is v_0 itself (the f32 program would copy it; a mean over one peer multiplies by 1)
+    float* S = P > 1 ? temp(P) : wide ? static_cast<float*>(out) : temp(0);
+    for (int p = 0; p < P && rc == FMI_OK; ++p) {
+        fin[p] = temp(p);
+        rc = launch_mx_dequantize(FMI_F32, P > 1 ? temp(p) : S, dtype, ins[p], static_cast<const uint8_t*>(in_scales[p]), n, s);
+    }
+    if (rc == FMI_OK && P > 1) {
+        if (wide) S = static_cast<float*>(out);
+        rc = reduce_tree_impl(op, FMI_F32, alg, S, fin.data(), P, rank, n, s);
+    }
+    if (rc == FMI_OK && !wide) rc = launch_mx_quantize(dtype, out, static_cast<uint8_t*>(out_scales), FMI_F32, S, n, s);
+    FMI_HIP_TRY(hipEventRecord(g_acc.free, s));
+    return rc;
+}
+
+}  // namespace fmi::dev
+
+int fmi_dev_reduce_tree_mx(int op, int dtype_arg, int alg, int out_dtype, void* out, void* out_scales, const void* const* ins,
+                           const void* const* in_scales, int P, int rank, size_t n, fmi_stream_t stream) {
+    return guarded("fmi_dev_reduce_tree_mx", [&]() -> int {
+        int dtype = 0;
+        if (int rc = mx_check_args("fmi_dev_reduce_tree_mx", op, dtype_arg, alg, out_dtype, out_scales, &dtype)) return rc;
+        if (int rc = check_peer_args(FMI_OP_SUM, dtype, P)) return rc;
+        if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
+        if (!out || !ins || !in_scales) return fail(FMI_ERR_INVALID, "null buffer");
+        for (int p = 0; p < P; ++p)
+            if (!ins[p] || !in_scales[p]) return fail(FMI_ERR_INVALID, "null input bucket or scale array");
+        if (int rc = require_device()) return rc;
+        return reduce_tree_mx(op, dtype, alg, out_dtype, out, out_scales, ins, in_scales, P, rank, n, resolve(stream));
+    });
+}
+
+int fmi_dev_mx_quantize(int dtype, void* out, void* out_scales, int src_dtype, const void* src, size_t n, fmi_stream_t stream) {
+    return guarded("fmi_dev_mx_quantize", [&]() -> int {
+        if (int rc = mx_check_convert("fmi_dev_mx_quantize", dtype, "src_dtype", src_dtype)) return rc;
+        if (n == 0) return FMI_OK;
+        if (!out || !out_scales || !src) return fail(FMI_ERR_INVALID, "fmi_dev_mx_quantize: null buffer (out, out_scales or src)");
+        if (int rc = require_device()) return rc;
+        return launch_mx_quantize(dtype, out, static_cast<uint8_t*>(out_scales), src_dtype, src, n, resolve(stream));
+    });
+}
+
+int fmi_dev_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const void* src_scales, size_t n, fmi_stream_t stream) {
+    return guarded("fmi_dev_mx_dequantize", [&]() -> int {
+        if (int rc = mx_check_convert("fmi_dev_mx_dequantize", dtype, "dst_dtype", dst_dtype)) return rc;
+        if (n == 0) return FMI_OK;
+        if (!dst || !src || !src_scales) return fail(FMI_ERR_INVALID, "fmi_dev_mx_dequantize: null buffer (dst, src or src_scales)");
+        if (int rc = require_device()) return rc;
+        return launch_mx_dequantize(dst_dtype, dst, dtype, src, static_cast<const uint8_t*>(src_scales), n, resolve(stream));
+    });
+}

@@ -12,6 +12,8 @@
 //   FMI_OP_AVG               fmi_fused_avg_*.hip, one per reduce algorithm (f32 f64 f16 bf16, the last two with f32 values too)
 //   scaled 8-bit sums        fmi_fused_fp8_scaled_*.hip, one per reduce algorithm (fmi_dev_reduce_tree_scaled: both 8-bit
 //                            floats, 8-bit and f32 output; their own entry, launch_fused_scaled below)
+//   MX 8-bit sums and means  fmi_fused_mx_*.hip, one per reduce algorithm (fmi_dev_reduce_tree_mx: both 8-bit floats, 8-bit
+//                            and f32 output; their own entry, launch_fused_mx below)
 // Everything else a call can be runs elsewhere (fmi_dev.hip): P beyond a variant's kernels and unaligned buckets as
 // blocks of fused programs, as widen / the f32 program / narrow, as the SUM program and the scale kernel
 // (fmi_scale.hip), or as pairwise passes in the program's order.
@@ -129,6 +131,15 @@ int launch_fused_scaled(int alg, int dtype, int out_dtype, int P, const PeerPtrs
         case sched::kReduce: return scaled_unit<sched::kReduce>(dtype, out_dtype, P, ptrs, sc, n, s);
         case sched::kReduceLtr: return scaled_unit<sched::kReduceLtr>(dtype, out_dtype, P, ptrs, sc, n, s);
         default: return fail(FMI_ERR_INVALID, "fused scaled launch: no kernel for algorithm " + std::to_string(alg));
+    }
+}
+
+int launch_fused_mx(int alg, int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s) {
+    switch (alg) {
+        case sched::kAllreduce: return mx_unit<sched::kAllreduce>(dtype, out_dtype, P, ptrs, mx, n, s);
+        case sched::kReduce: return mx_unit<sched::kReduce>(dtype, out_dtype, P, ptrs, mx, n, s);
+        case sched::kReduceLtr: return mx_unit<sched::kReduceLtr>(dtype, out_dtype, P, ptrs, mx, n, s);
+        default: return fail(FMI_ERR_INVALID, "fused MX launch: no kernel for algorithm " + std::to_string(alg));
     }
 }
 

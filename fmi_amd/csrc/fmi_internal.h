@@ -240,6 +240,33 @@ int launch_amax_fold(float* amax, const uint32_t* words, int count, hipStream_t 
 int scaled_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype, int* dtype);
 int reduce_tree_scaled(int dtype, int alg, int out_dtype, void* out, const void* const* ins, const float* in_scales,
                        const float* out_scale, float* amax, int P, int rank, size_t n, hipStream_t s);
+// fmi_dev_reduce_tree_mx (include/fmi_dev.h): the sum or mean of block-scaled (MX) 8-bit float buckets. What its fused
+// kernels take beside the peer pointers, the kernel argument's 2 P + 2 pointers in all: in_scales[t] the E8M0 scale
+// bytes of ptrs.in[t] (a kReduce call's caller rotates them with the inputs), out_scales the result's (unused with an
+// f32 output), r the mean's factor fl32(1 / P), or 1.0f for a sum.
+struct MxArgs {
+    const uint8_t* in_scales[sched::kMaxFusedPeers];
+    uint8_t* out_scales;
+    float r;
+};
+// The fused MX kernels (fmi_fused.hip -> fmi_fused_mx_*.hip): 2 <= P <= 16, the element buckets 16-B aligned, the
+// scale arrays of any alignment. alg, dtype, out_dtype, ptrs as launch_fused_scaled's.
+int launch_fused_mx(int alg, int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
+// One translation unit's MX kernels (algorithm ALG, P = 2..16, both dtypes, both outputs): defined in fmi_mx_impl.h,
+// instantiated by one fmi_fused_mx_*.hip each.
+using MxUnit = int(int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
+template <int ALG>
+MxUnit mx_unit;
+// fmi_dev_mx_dequantize / fmi_dev_mx_quantize (fmi_mx.hip), any alignment, one launch each. dtype: FMI_F8E4M3 /
+// FMI_F8E5M2; dst_dtype / src_dtype: FMI_F32, FMI_F16 or FMI_BF16 (FMI_ERR_INVALID otherwise).
+int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s);
+int launch_mx_quantize(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s);
+// The host-side checks of fmi_dev_reduce_tree_mx's op, dtype argument, alg, out_dtype and out_scales (fmi_dev.hip),
+// shared with fmi_comm_allreduce_mx; *dtype: the storage dtype. And the call after its validation: the comm call's
+// shard step.
+int mx_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype, const void* out_scales, int* dtype);
+int reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* out_scales, const void* const* ins,
+                   const void* const* in_scales, int P, int rank, size_t n, hipStream_t s);
 // kReducePartials for any P and any alignment / dtype (fused kernel where it applies, pairwise passes otherwise):
 // outs[t] = the value transformed peer t of reduce_no_order holds in its sendbuf at the end
 // (src/comm/PeerToPeer.cpp:66-78); ins in transformed order. Defined in fmi_dev.hip.

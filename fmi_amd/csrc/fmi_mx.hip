@@ -1,0 +1,90 @@
+// The kernels of the MX calls beside the fused ones (include/fmi_dev.h): fmi_dev_mx_quantize and fmi_dev_mx_dequantize,
+// which are also what a fmi_dev_reduce_tree_mx call beyond the fused kernels (P = 1, P > 16, unaligned buckets) runs
+// around the library's own FMI_F32 program.
+//   dequantize   dst[i] = narrow_dst(fl32(widen(src[i]) * scale32(scales[i / 32])))
+//   quantize     per block of 32: A = umax bits(|S|), e_out = mx_scale_byte(A), out = narrow(fl32(S * 2^(127 - e_out)))
+// Any alignment: one element per thread and step, grid-stride; a block of 32 elements is one half of a wave, so its
+// amax is five shuffles inside the half. The waves' loops are uniform (a wave leaves only when all its elements are
+// beyond n), so every shuffle has all its lanes. These are the fallback's passes, not a hot path.
+#include "fmi_mx_impl.h"
+
+namespace fmi::dev {
+namespace {
+
+constexpr unsigned kBlock = 256;  // a multiple of 64: waves start on block boundaries
+constexpr size_t kGridCap = size_t(1) << 20;
+
+// T: the 8-bit storage type; D: float, _Float16 or __bf16.
+template <class T, class D>
+__global__ void __launch_bounds__(kBlock) mx_dequantize_kernel(D* dst, const T* src, const uint8_t* scales, size_t n) {
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        Lanes<float, 1> v;
+        v.v[0] = fp8_widen(src[i]) * mx_scale32(scales[i / 32]);
+        dst[i] = to_storage<D>(v).v[0];
+    }
+}
+
+template <class T, class S>
+__global__ void __launch_bounds__(kBlock) mx_quantize_kernel(T* out, uint8_t* out_scales, const S* src, size_t n) {
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    const unsigned lane = threadIdx.x % 64;
+    // `wave0`: the first element of this wave's 64 (two blocks); the loop's condition is the wave's, not the lane's
+    for (size_t wave0 = static_cast<size_t>(blockIdx.x) * blockDim.x + (threadIdx.x - lane); wave0 < n; wave0 += stride) {
+        const size_t i = wave0 + lane;
+        const bool have = i < n;
+        float x = 0.0f;
+        if (have) {
+            Lanes<S, 1> raw;
+            raw.v[0] = src[i];
+            x = to_value<float>(raw).v[0];
+        }
+        uint32_t A = mx_abs_bits(x);  // 0 beyond the bucket
+#pragma unroll
+        for (int d = 16; d > 0; d >>= 1) A = max(A, static_cast<uint32_t>(__shfl_xor(static_cast<int>(A), d, 64)));
+        const uint32_t e_out = mx_scale_byte<T>(A);
+        const float y = x * mx_inv_scale(e_out);
+        if (have) {
+            out[i] = e_out == 255u ? T{0x7F} : fp8_narrow<T>(y);
+            if (lane % 32 == 0) out_scales[i / 32] = static_cast<uint8_t>(e_out);
+        }
+    }
+}
+
+unsigned grid_of(size_t n) { return static_cast<unsigned>(std::min(grid_for(n, kBlock), kGridCap)); }
+
+// f.template operator()<D>() for the non-MX side of a conversion: FMI_F32, FMI_F16 or FMI_BF16.
+template <class F>
+int with_wide_dtype(const char* who, const char* what, int dtype, F&& f) {
+    switch (dtype) {
+        case FMI_F32: return f.template operator()<float>();
+        case FMI_F16: return f.template operator()<_Float16>();
+        case FMI_BF16: return f.template operator()<__bf16>();
+        default:
+            return fail(FMI_ERR_INVALID, std::string(who) + ": " + what + " " + std::to_string(dtype) + " must be FMI_F32, FMI_F16 or FMI_BF16");
+    }
+}
+
+}  // namespace
+
+int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s) {
+    if (n == 0) return FMI_OK;
+    return with_dtype<kTierFp8>(dtype, [&]<class T>() -> int {
+        return with_wide_dtype("fmi_dev_mx_dequantize", "dst_dtype", dst_dtype, [&]<class D>() -> int {
+            mx_dequantize_kernel<T, D><<<grid_of(n), kBlock, 0, s>>>(static_cast<D*>(dst), static_cast<const T*>(src), scales, n);
+            return check_launch("MX dequantize kernel launch");
+        });
+    });
+}
+
+int launch_mx_quantize(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s) {
+    if (n == 0) return FMI_OK;
+    return with_dtype<kTierFp8>(dtype, [&]<class T>() -> int {
+        return with_wide_dtype("fmi_dev_mx_quantize", "src_dtype", src_dtype, [&]<class S>() -> int {
+            mx_quantize_kernel<T, S><<<grid_of(n), kBlock, 0, s>>>(static_cast<T*>(out), out_scales, static_cast<const S*>(src), n);
+            return check_launch("MX quantize kernel launch");
+        });
+    });
+}
+
+}  // namespace fmi::dev

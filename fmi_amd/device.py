@@ -49,6 +49,9 @@ class DType(enum.IntEnum):
     BF16 = 11
     F8E4M3 = 12
     F8E5M2 = 13
+    # The scale bytes of an MX bucket (E8M0: 2^(e - 127), 255 = NaN), one per 32 elements, over np.uint8. A label of this
+    # binding alone (include/fmi_dev.h reserves the value): no C-ABI call takes it as an element dtype.
+    F8E8M0 = 14
 
 
 # fmi_dev.h's FMI_ACC_F32: ORed into the dtype argument of a P-way call on F16 / BF16 / F8E4M3 / F8E5M2 buckets, the program's values
@@ -98,7 +101,7 @@ NP_DTYPE = {DType.F32: np.float32, DType.F64: np.float64, DType.I32: np.int32, D
             DType.U16: np.uint16, DType.F16: np.float16}
 # numpy has no bfloat16 and no 8-bit floats: a BF16 bucket moves its elements' raw bits as np.uint16, an F8E4M3 /
 # F8E5M2 bucket as np.uint8 (np.uint8 alone keeps meaning U8)
-_HOST_DTYPE = {**NP_DTYPE, DType.BF16: np.uint16, DType.F8E4M3: np.uint8, DType.F8E5M2: np.uint8}
+_HOST_DTYPE = {**NP_DTYPE, DType.BF16: np.uint16, DType.F8E4M3: np.uint8, DType.F8E5M2: np.uint8, DType.F8E8M0: np.uint8}
 
 
 def dtype_of(arr_or_dtype) -> DType:
@@ -413,6 +416,71 @@ def reduce_tree_scaled(alg: Alg, out: Bucket, ins: Sequence[Bucket], in_scales: 
     _lib.call("fmi_dev_reduce_tree_scaled", int(Op.SUM), int(dtype), int(alg), int(out.dtype), out.ptr, _ptr_array(ins),
               _f32_word(in_scales, "in_scales", len(ins)), _f32_word(out_scale, "out_scale"), _f32_word(amax, "amax"),
               len(ins), rank, out.n, _sptr(stream))
+
+
+MX_BLOCK = 32  # elements per scale byte of an MX bucket
+
+
+def mx_blocks(n: int) -> int:
+    """The number of scale bytes of an MX bucket of n elements: ceil(n / 32)."""
+    return (int(n) + MX_BLOCK - 1) // MX_BLOCK
+
+
+def _mx_scales(b, what: str, n: int) -> int:
+    if not isinstance(b, Bucket) or b.dtype not in (DType.F8E8M0, DType.U8):
+        raise ValueError(f"{what} must be an F8E8M0 (or U8) bucket of scale bytes")
+    if b.n != mx_blocks(n):
+        raise ValueError(f"{what} must hold ceil(n / 32) = {mx_blocks(n)} scale bytes for {n} elements, got {b.n}")
+    return b.ptr
+
+
+def _mx_elements(who: str, what: str, b: Bucket) -> DType:
+    if b.dtype not in (DType.F8E4M3, DType.F8E5M2):
+        raise ValueError(f"{who} needs F8E4M3 or F8E5M2 {what}, got {DType(b.dtype).name}")
+    return b.dtype
+
+
+def reduce_tree_mx(op: Op, alg: Alg, out: Bucket, out_scales: Optional[Bucket], ins: Sequence[Bucket],
+                   in_scales: Sequence[Bucket], rank: int = 0, stream=None) -> None:
+    """The sum (Op.SUM) or mean (Op.AVG) of block-scaled (MX) F8E4M3 / F8E5M2 buckets (fmi_dev_reduce_tree_mx): every
+    input element times its block's E8M0 scale in f32, the f32 SUM program of `alg`, then either stored as F32 (`out` an
+    F32 bucket, out_scales None) or requantized: per block of 32 the smallest power-of-two scale that brings the block's
+    largest magnitude within the element type, into `out_scales`, and the scaled sum narrowed into `out`. in_scales[p]
+    and out_scales are F8E8M0 buckets of ceil(n / 32) bytes. One fused kernel at 2..16 peers on 16-B aligned element
+    buckets; bit-exact and deterministic."""
+    if not ins:
+        raise ValueError("need at least one peer bucket")
+    dtype = _mx_elements("reduce_tree_mx", "input buckets", ins[0])
+    _check_peers(ins[0], ins)
+    if out.n != ins[0].n or out.dtype not in (dtype, DType.F32):
+        raise ValueError("reduce_tree_mx: `out` must hold the inputs' length in their dtype or in F32")
+    if len(in_scales) != len(ins):
+        raise ValueError("reduce_tree_mx: one in_scales bucket per input")
+    if out.dtype != DType.F32 and out_scales is None:
+        raise ValueError("reduce_tree_mx: out_scales is missing: only an F32 output has no scale bytes")
+    sptrs = (ctypes.c_void_p * len(ins))(*[_mx_scales(b, f"in_scales[{p}]", out.n) for p, b in enumerate(in_scales)])
+    _lib.call("fmi_dev_reduce_tree_mx", int(op), int(dtype), int(alg), int(out.dtype), out.ptr,
+              None if out_scales is None else _mx_scales(out_scales, "out_scales", out.n), _ptr_array(ins), sptrs,
+              len(ins), rank, out.n, _sptr(stream))
+
+
+def mx_quantize(out: Bucket, out_scales: Bucket, src: Bucket, stream=None) -> None:
+    """An F32 / F16 / BF16 bucket into an MX bucket (fmi_dev_mx_quantize): per block of 32 elements the scale byte of
+    reduce_tree_mx, into `out_scales`, and the elements narrowed under it into `out` (F8E4M3 / F8E5M2)."""
+    dtype = _mx_elements("mx_quantize", "output bucket", out)
+    if src.dtype not in (DType.F32, DType.F16, DType.BF16) or src.n != out.n:
+        raise ValueError("mx_quantize: `src` must be an F32, F16 or BF16 bucket of out's length")
+    _lib.call("fmi_dev_mx_quantize", int(dtype), out.ptr, _mx_scales(out_scales, "out_scales", out.n), int(src.dtype),
+              src.ptr, out.n, _sptr(stream))
+
+
+def mx_dequantize(dst: Bucket, src: Bucket, src_scales: Bucket, stream=None) -> None:
+    """An MX bucket into an F32 / F16 / BF16 bucket (fmi_dev_mx_dequantize): dst = narrow_dst(widen(src) * scale)."""
+    dtype = _mx_elements("mx_dequantize", "source bucket", src)
+    if dst.dtype not in (DType.F32, DType.F16, DType.BF16) or dst.n != src.n:
+        raise ValueError("mx_dequantize: `dst` must be an F32, F16 or BF16 bucket of src's length")
+    _lib.call("fmi_dev_mx_dequantize", int(dst.dtype), dst.ptr, int(dtype), src.ptr, _mx_scales(src_scales, "src_scales", src.n),
+              src.n, _sptr(stream))
 
 
 def mean_scale(inout: Bucket, P: int, n: Optional[int] = None, stream=None) -> None:

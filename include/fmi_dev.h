@@ -139,6 +139,9 @@ typedef enum {
     FMI_U32 = 4, FMI_U64 = 5, FMI_I8 = 6, FMI_U8 = 7, FMI_I16 = 8, FMI_U16 = 9,
     FMI_F16 = 10, FMI_BF16 = 11, FMI_F8E4M3 = 12, FMI_F8E5M2 = 13
 } fmi_dtype_t;
+/* Reserved, NOT an fmi_dtype_t: FMI_F8E8M0 = 14 is the label the Python binding gives the scale bytes of an MX bucket
+ * (DType.F8E8M0, bytes over np.uint8; fmi_dev_reduce_tree_mx below). No C-ABI call takes it as a dtype: every one
+ * answers "unknown dtype". The scale arrays of the MX calls are plain byte pointers. */
 
 /* f32 accumulation: a modifier bit on the dtype ARGUMENT of a call, valid only on FMI_F16, FMI_BF16, FMI_F8E4M3 and
  * FMI_F8E5M2 (with any other dtype: FMI_ERR_INVALID naming the dtype). The buckets keep their storage type; a P-way
@@ -363,6 +366,49 @@ int fmi_dev_reduce_tree_scaled(int op, int dtype, int alg, int out_dtype, void* 
                                const float* in_scales, const float* out_scale, float* amax, int P, int rank, size_t n,
                                fmi_stream_t stream);
 
+/* Block-scaled (MX) 8-bit float buckets: the OCP Microscaling layout, one power-of-two scale byte (E8M0) per 32
+ * consecutive elements. An MX bucket of n elements is two arrays: n element bytes (FMI_F8E4M3 or FMI_F8E5M2, the
+ * encodings above) and ceil(n / 32) scale bytes; block b covers elements 32 b .. min(32 b + 31, n - 1), so the last
+ * block may be ragged. A scale byte e decodes to the f32 scale32(e):
+ *     e in 1..254: the f32 with bits e << 23, 2^(e - 127);   e = 0: bits 0x00400000, 2^-127 (an f32 subnormal);
+ *     e = 255: NaN                                            (torch.float8_e8m0fnu -> float32 on every byte)
+ * fmi_dev_reduce_tree_mx: the sum or mean of P MX buckets in one pass. Per element i of block b:
+ *     v_p   = fl32( widen(x_p[i]) * scale32(e_p[b]) )      exact, or +-inf on overflow, or NaN (e = 255)
+ *     S     = F32_program_alg( v_0 .. v_{P-1} )             the FMI_F32 SUM program of `alg`, the same bracketing
+ *     S     = fl32( S * r_P )                               FMI_OP_AVG only, r_P = fl32(1 / P) as at FMI_OP_AVG
+ *     out_dtype == FMI_F32:   out[i] = S                    no output scales
+ *     out_dtype == dtype:     per block b
+ *         A      = umax over the block's existing elements of bits(|S|)     unsigned compare, a NaN wins
+ *         f, m   = A >> 23, A & 0x7FFFFF
+ *         e_out  = 255                                   if f == 255 (the block holds an inf or a NaN)
+ *                = max( f - EMAX + (m > 0x600000), 0 )   otherwise;  EMAX = 8 for E4M3, 15 for E5M2
+ *         out_scales[b] = e_out
+ *         out[i] = 0x7F                                          if e_out == 255 (the whole block is NaN, as MX says)
+ *                = narrow( fl32( S * bits((254 - e_out) << 23) ) )   otherwise: the non-saturating narrowing above
+ * e_out is the smallest power of two that brings the block's largest magnitude to at most the largest finite element
+ * (448 = 1.75 * 2^8, 57344 = 1.75 * 2^15: mantissa bits 0x600000): the round-up rule of MXFP8 recipes, not the floor of
+ * the OCP example, under which elements in (448, 512) * 2^E would need a saturating narrowing. With round-up no
+ * element of a finite block overflows, nothing is clipped at the block's maximum, e_out stays within 0..247 (0..240)
+ * and the inverse scale is a normal f32. Every operation is round-to-nearest-even with subnormals kept and no
+ * contraction; the result does not depend on any order beyond the program's bracketing (deterministic, no atomics).
+ * Valid: op FMI_OP_SUM or FMI_OP_AVG (PROD / MAX / MIN: FMI_ERR_INVALID); alg FMI_ALG_ALLREDUCE, _REDUCE or _REDUCE_LTR
+ * with `rank` as in fmi_dev_reduce_tree (the scans: FMI_ERR_INVALID); dtype one of the two 8-bit floats (FMI_ACC_F32 is
+ * accepted and dropped); out_dtype == dtype or FMI_F32; out_scales may be NULL only with FMI_F32; P >= 1, and P = 1 is
+ * NOT a copy: it requantizes. All of it is checked on the host before a device is needed. ins[p] / in_scales[p]: peer
+ * p's elements and scale bytes. out may alias an ins[p], and out_scales an in_scales[p], where out_dtype == dtype.
+ * 2 <= P <= 16 with the element buckets 16-B aligned (scale arrays: any alignment): ONE fused kernel, graph-capturable,
+ * no atomics, no temporaries. Any other call (P = 1, P > 16, unaligned buckets) dequantizes every input into an f32
+ * temporary (FMI_ACC_F32's allocation: not capturable), runs the library's own FMI_F32 program and quantizes: the same
+ * bits by construction. Additive: fmi_abi_version() stays 1. */
+int fmi_dev_reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* out_scales, const void* const* ins,
+                           const void* const* in_scales, int P, int rank, size_t n, fmi_stream_t stream);
+/* The fallback's two kernels made public, as fmi_dev_convert is. The non-MX side (src_dtype / dst_dtype) is FMI_F32,
+ * FMI_F16 or FMI_BF16. Quantize: the out_dtype == dtype branch above applied to S = widen(src[i]) (exact). Dequantize:
+ * dst[i] = narrow_dst( fl32( widen(src[i]) * scale32(src_scales[i / 32]) ) ). Any alignment, n = 0 succeeds, one launch
+ * each, graph-capturable. */
+int fmi_dev_mx_quantize(int dtype, void* out, void* out_scales, int src_dtype, const void* src, size_t n, fmi_stream_t stream);
+int fmi_dev_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const void* src_scales, size_t n, fmi_stream_t stream);
+
 /* Peer-axis inclusive scan of P device buckets: outs[k] = x0 (+) ... (+) xk with the evaluation order
  * of `alg` (FMI_ALG_SCAN or FMI_ALG_SCAN_LTR). Replaces reference PeerToPeer::scan_no_order / scan_ltr
  * (src/comm/PeerToPeer.cpp:154-184, :141-152) and Communicator::scan (include/Communicator.h:135-150)
@@ -475,6 +521,17 @@ int fmi_comm_allreduce(fmi_comm_t comm, int op, int dtype, int alg, int path, co
 int fmi_comm_allreduce_scaled(fmi_comm_t comm, int op, int dtype, int alg, int out_dtype, const void* send,
                               const float* in_scale, void* recv, const float* out_scale, float* amax, size_t n,
                               fmi_stream_t stream);
+/* The sharded allreduce of MX buckets (fmi_dev_reduce_tree_mx above): path TREE, unpipelined, on every transport. op:
+ * FMI_OP_SUM or FMI_OP_AVG; dtype, out_dtype as there; alg: FMI_ALG_ALLREDUCE or FMI_ALG_REDUCE_LTR. `send` holds n
+ * elements and send_scales ceil(n / 32) scale bytes; `recv` n elements of out_dtype and recv_scales ceil(n / 32) bytes
+ * (NULL only with FMI_F32). The element shards travel as they do in fmi_comm_allreduce_scaled; the scale bytes travel
+ * in a second all-to-all of shard / 32 bytes per shard: shards are multiples of 64 elements, so no block is split
+ * between owners. Each owner runs fmi_dev_reduce_tree_mx at P = N, rank 0, on its shard's TRUE length (padding never
+ * enters a block's amax); element and scale shards are then all-gathered. Every rank's recv / recv_scales is the
+ * definition over the ranks' buckets in rank order. send / send_scales are not modified. A one-rank communicator runs
+ * the P = 1 form. */
+int fmi_comm_allreduce_mx(fmi_comm_t comm, int op, int dtype, int alg, int out_dtype, const void* send,
+                          const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream);
 /* Host-ingress allreduce (BASELINE config C5): `send` / `recv` are HOST buckets, i.e. the channel recv
  * buffers FMI's transports deliver into (reference src/comm/Direct.cpp:36-45, PeerToPeer.cpp:110-129).
  * The bucket streams through the GPU in chunks of `chunk` elements (0 = FMI_TUNE_HOST_CHUNK bytes):

@@ -6,11 +6,14 @@ remarks as tools/half_resource_usage.py does it (each unit compiled device-only 
 
     python3 tools/fp8_resource_usage.py                  # every fp8_acc_kernel at P = 8 and P = 16, and the conversions
     python3 tools/fp8_resource_usage.py --all            # every P
+    python3 tools/fp8_resource_usage.py --mx             # the fused MX units (fmi_fused_mx_*.hip) and fmi_mx.hip instead:
+                                                         # fp8_mx_kernel at P = 8 and 16, the quantize / dequantize kernels
     python3 tools/fp8_resource_usage.py --isa            # instruction counts of the 8-way allreduce SUM kernels' loop
                                                          # (e4m3, e5m2 and the bf16 acc32 kernel beside them)
 
 Lines: fp8_acc_kernel<op, dtype, alg, P, scan>: vgpr .. agpr .. scratch .. occupancy ..
-(alg: 0 allreduce, 1 reduce, 2 reduce_ltr, 3 scan, 4 scan_ltr, 8 reduce partials).
+(alg: 0 allreduce, 1 reduce, 2 reduce_ltr, 3 scan, 4 scan_ltr, 8 reduce partials);
+fp8_mx_kernel<dtype, alg, P, out32>, mx_quantize_kernel<dtype, source>, mx_dequantize_kernel<dtype, destination>.
 """
 import argparse
 import concurrent.futures
@@ -36,6 +39,12 @@ def describe(mangled):
         types = re.findall(r"NS\d*_(6f8e4m3|6f8e5m2)E|S\d*_|(DF16_|DF16b|f)", m.group(1))
         names = [FP8.get(a) or OTHER.get(b) or "same" for a, b in types]
         return "convert_kernel", 0, ", ".join(names + ["nt" if m.group(2) == "1" else "plain"])
+    m = re.search(r"13fp8_mx_kernelINS\d*_(6f8e4m3|6f8e5m2)ELi(\d+)ELi(\d+)ELb([01])EEE", mangled)
+    if m:
+        return "fp8_mx_kernel", int(m.group(3)), f"{FP8[m.group(1)]}, {m.group(2)}, {m.group(3)}, {'true' if m.group(4) == '1' else 'false'}"
+    m = re.search(r"\d+(mx_quantize_kernel|mx_dequantize_kernel)INS\d*_(6f8e4m3|6f8e5m2)E(DF16_|DF16b|f)EE", mangled)
+    if m:
+        return m.group(1), 0, f"{FP8[m.group(2)]}, {OTHER[m.group(3)]}"
     return None
 
 
@@ -73,20 +82,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--isa", action="store_true", help="instruction counts of the 8-way allreduce kernels instead")
     ap.add_argument("--all", action="store_true", help="every P, not P = 8 and 16 alone")
+    ap.add_argument("--mx", action="store_true", help="the MX units (fmi_fused_mx_*.hip, fmi_mx.hip) instead")
     ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 8))
     a = ap.parse_args()
     if a.isa:
         return isa()
-    srcs = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "fmi_fused_fp8_acc32_*.hip"))) + ["fmi_acc32_convert.hip"]
+    if a.mx:
+        srcs = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "fmi_fused_mx_*.hip"))) + ["fmi_mx.hip"]
+    else:
+        srcs = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "fmi_fused_fp8_acc32_*.hip"))) + ["fmi_acc32_convert.hip"]
     with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
         kernels = [k for t in ex.map(remarks, srcs) for k in parse(t)]
     shown = spilled = 0
     for k in kernels:
         d = describe(k["name"])
-        if d is None:
+        if d is None or (d[0].endswith("mx_kernel") or d[0].startswith("mx_")) != a.mx:
             continue
         spilled += k["scratch"] != 0
-        if d[0] == "fp8_acc_kernel" and not a.all and d[1] not in (8, 16):
+        if d[0] in ("fp8_acc_kernel", "fp8_mx_kernel") and not a.all and d[1] not in (8, 16):
             continue
         shown += 1
         print(f"{d[0]}<{d[2]}>: vgpr {k['vgpr']} agpr {k['agpr']} scratch {k['scratch']} occupancy {k['occ']}")

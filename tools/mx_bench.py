@@ -1,0 +1,106 @@
+"""The fused MX kernel (fmi_dev_reduce_tree_mx) beside the per-tensor scaled kernel and its own fallback, on one GPU,
+timed with events, by the protocol of tools/fp8_scaled_bench.py:
+
+  scaled            reduce_tree_scaled, out = the inputs' dtype, amax = NULL (the yardstick: its code is not the MX call's)
+  mx                reduce_tree_mx SUM, out = the inputs' dtype with scale bytes: the fused kernel
+  mx_f32            the same with an F32 output and no output scales
+  mx_fallback       reduce_tree_mx on element buckets one byte off 16-B alignment: dequantize x P, the f32 program,
+                    quantize (the path of P = 1, P > 16 and unaligned buckets)
+
+P = 8 peers of 256 MiB of elements each (8 MiB of scale bytes per peer), the element buckets (and the 8-bit output) of a
+set carved as one group (fmi_dev_alloc_group); three rotating sets, so that no bucket returns within 256 MB of the
+Infinity Cache; the kernels interleaved in one process, three passes. One JSON line per kernel: element rate and bytes/s
+per pass and their median, the fraction of 8 TB/s (algorithmic bytes, scale bytes counted: P * (n + n / 32) in,
+n + n / 32 or 4 n out), the ratio of the ELEMENT rate to the yardstick's of the same pass, and the yardstick's own
+spread over the passes.
+
+    python3 tools/mx_bench.py [--kind e4m3] [--label NAME] [--out profiles/mx_bench.jsonl]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np  # noqa: E402
+
+import fmi_amd  # noqa: E402
+from fmi_amd import Alg, Bucket, DType, Op  # noqa: E402
+from half_kernels import MIB, PASSES, emit, timed  # noqa: E402
+
+ROWS = ("scaled", "mx", "mx_f32", "mx_fallback")  # the first is the yardstick
+PEAK = 8e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", default="e4m3", choices=("e4m3", "e5m2"))
+    ap.add_argument("--mib", type=int, default=256, help="element bytes per input bucket")
+    ap.add_argument("--peers", type=int, default=8)
+    ap.add_argument("--sets", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=24, help="timed launches per fused kernel and pass")
+    ap.add_argument("--fallback-iters", type=int, default=3, help="timed calls of the fallback per pass (about ten times the bytes)")
+    ap.add_argument("--rows", default=",".join(ROWS), help="which rows to run; the yardstick always runs")
+    ap.add_argument("--label", default="tree")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+    fmi_amd.init(0)
+    dt = DType.F8E4M3 if args.kind == "e4m3" else DType.F8E5M2
+    P, n, S = args.peers, args.mib * MIB, args.sets
+    nb = fmi_amd.mx_blocks(n)
+    rows = [r for r in ROWS if r == ROWS[0] or r in args.rows.split(",")]
+    # 16 spare bytes per bucket: the fallback's inputs are the same allocations one byte in
+    groups = [Bucket.group(P + 1, n + 16, dt) for _ in range(S)]
+    aligned = [[b.view(0, n) for b in g] for g in groups]
+    shifted = [[b.view(1, n) for b in g] for g in groups]
+    wide = [Bucket(n, np.float32) for _ in range(S)]
+    rng = np.random.default_rng(3)
+    scale_sets = []
+    for g in aligned:
+        for p in range(P):
+            g[p].fill_synthetic(11, p)
+        scale_sets.append([Bucket(nb, DType.F8E8M0) for _ in range(P + 1)])
+        for b in scale_sets[-1][:P]:
+            b.upload(rng.integers(120, 135, nb).astype(np.uint8))
+    p_ = np.arange(P, dtype=np.float64)
+    scales = Bucket.from_numpy(((1.0 + np.mod(0.37 * p_, 1.0)) / 3.0 * 2.0 ** (np.mod(p_, 5) - 2)).astype(np.float32))
+    t = Bucket.from_numpy(np.array([0.7123], np.float32))
+    fmi_amd.sync()
+    launches = {
+        "scaled": lambda k: fmi_amd.reduce_tree_scaled(Alg.ALLREDUCE, aligned[k % S][P], aligned[k % S][:P], scales, t),
+        "mx": lambda k: fmi_amd.reduce_tree_mx(Op.SUM, Alg.ALLREDUCE, aligned[k % S][P], scale_sets[k % S][P], aligned[k % S][:P], scale_sets[k % S][:P]),
+        "mx_f32": lambda k: fmi_amd.reduce_tree_mx(Op.SUM, Alg.ALLREDUCE, wide[k % S], None, aligned[k % S][:P], scale_sets[k % S][:P]),
+        "mx_fallback": lambda k: fmi_amd.reduce_tree_mx(Op.SUM, Alg.ALLREDUCE, shifted[k % S][P], scale_sets[k % S][P], shifted[k % S][:P], scale_sets[k % S][:P]),
+    }
+    algo = {"scaled": P * n + n, "mx": P * (n + nb) + n + nb, "mx_f32": P * (n + nb) + 4 * n, "mx_fallback": P * (n + nb) + n + nb}
+    iters = {r: args.fallback_iters if r == "mx_fallback" else args.iters for r in ROWS}
+    ms = {r: [] for r in rows}
+    for _ in range(PASSES):
+        for r in rows:
+            ms[r].append(timed(launches[r], iters[r], S))
+    spread = lambda xs: round((max(xs) - min(xs)) / statistics.median(xs), 4)  # noqa: E731
+    elem = {r: [n / (m * 1e-3) for m in ms[r]] for r in rows}
+    lines = []
+    for r in rows:
+        byte_rate = [algo[r] / (m * 1e-3) for m in ms[r]]
+        ratios = [a / b for a, b in zip(elem[r], elem[ROWS[0]])]
+        lines.append({"tool": "tools/mx_bench.py", "label": args.label, "inflight_kib": fmi_amd.tune_get(fmi_amd.Tune.FUSED_INFLIGHT_KIB),
+                      "kernel": f"tree{P} {args.kind} {r}", "elements_per_peer": n, "algorithmic_bytes": algo[r],
+                      "iters_per_pass": iters[r], "passes": PASSES, "rotating_sets": S, "ms_per_pass": [round(m, 4) for m in ms[r]],
+                      "Gelem_s_per_pass": [round(x / 1e9, 2) for x in elem[r]], "Gelem_s": round(statistics.median(elem[r]) / 1e9, 2),
+                      "GB_s_per_pass": [round(x / 1e9, 1) for x in byte_rate], "GB_s": round(statistics.median(byte_rate) / 1e9, 1),
+                      "fraction_of_8TBs": round(statistics.median(byte_rate) / PEAK, 4), "spread": spread(byte_rate),
+                      "yardstick": f"tree{P} {args.kind} {ROWS[0]}, same passes, element rate",
+                      "element_rate_ratio_to_scaled_per_pass": [round(x, 4) for x in ratios],
+                      "element_rate_ratio_to_scaled": round(statistics.median(ratios), 4), "scaled_spread": spread(elem[ROWS[0]]),
+                      "timing": "two HIP events around back-to-back launches on the library stream"})
+    emit(lines, args.out)
+    for b in [b for g in groups for b in g] + wide + [b for s in scale_sets for b in s] + [scales, t]:
+        b.free()
+    fmi_amd.sync()
+
+
+if __name__ == "__main__":
+    main()
