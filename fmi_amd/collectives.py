@@ -39,6 +39,9 @@ _TORCH_DTYPE = {torch.float32: DType.F32, torch.float64: DType.F64, torch.int32:
 for _name, _dt in (("float8_e4m3fn", DType.F8E4M3), ("float8_e5m2", DType.F8E5M2)):
     if hasattr(torch, _name):
         _TORCH_DTYPE[getattr(torch, _name)] = _dt
+# MXFP4: two E2M1 elements per tensor element; reduce_tree_mx alone takes it (the library refuses it anywhere else)
+if hasattr(torch, "float4_e2m1fn_x2"):
+    _TORCH_DTYPE[torch.float4_e2m1fn_x2] = DType.F4E2M1
 _FLOAT_DTYPES = tuple(t for t, d in _TORCH_DTYPE.items() if d in (DType.F32, DType.F64, DType.F16, DType.BF16, DType.F8E4M3, DType.F8E5M2))
 _REDUCE_OP = {Op.SUM: dist.ReduceOp.SUM, Op.PROD: dist.ReduceOp.PRODUCT, Op.MAX: dist.ReduceOp.MAX,
               Op.MIN: dist.ReduceOp.MIN, Op.AVG: dist.ReduceOp.AVG}
@@ -106,12 +109,17 @@ class HipEngine:
                        ins: Sequence[torch.Tensor], in_scales: Sequence[torch.Tensor], rank: int = 0) -> None:
         """The sum or mean of block-scaled (MX) float8 tensors (fmi_dev_reduce_tree_mx): `ins` are float8_e4m3fn /
         float8_e5m2 tensors, `in_scales` their float8_e8m0fnu (or uint8) scale tensors of ceil(n / 32) elements; `out` is
-        a tensor of the inputs' dtype with `out_scales`, or of float32 with out_scales None."""
+        a tensor of the inputs' dtype with `out_scales`, or of float32 with out_scales None. MXFP4: `ins` are
+        float4_e2m1fn_x2 tensors (two elements per tensor element, so n = 2 * numel and a float32 `out` holds 2 * numel
+        values)."""
         import ctypes
         dtype = _dtype(ins[0])
-        if dtype not in (DType.F8E4M3, DType.F8E5M2):
-            raise TypeError(f"reduce_tree_mx needs float8_e4m3fn or float8_e5m2 inputs, got {ins[0].dtype}")
-        if any(t.dtype != ins[0].dtype or t.numel() != out.numel() or not t.is_contiguous() for t in ins):
+        if dtype not in (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1):
+            raise TypeError(f"reduce_tree_mx needs float8_e4m3fn, float8_e5m2 or float4_e2m1fn_x2 inputs, got {ins[0].dtype}")
+        per = 2 if dtype == DType.F4E2M1 else 1  # elements per tensor element
+        n = per * ins[0].numel()
+        if any(t.dtype != ins[0].dtype or t.numel() != ins[0].numel() or not t.is_contiguous() for t in ins) or \
+                out.numel() * (per if out.dtype == ins[0].dtype else 1) != n:
             raise ValueError("reduce_tree_mx: contiguous inputs of one dtype and of out's length")
         if out.dtype not in (ins[0].dtype, torch.float32) or not out.is_contiguous():
             raise ValueError("reduce_tree_mx: `out` is a contiguous tensor of the inputs' dtype or of float32")
@@ -120,7 +128,7 @@ class HipEngine:
         if out.dtype != torch.float32 and out_scales is None:
             raise ValueError("reduce_tree_mx: out_scales is missing: only a float32 output has no scale bytes")
         scale_types = tuple(getattr(torch, k) for k in ("float8_e8m0fnu", "uint8") if hasattr(torch, k))
-        blocks = (out.numel() + 31) // 32
+        blocks = (n + 31) // 32
         named = [(f"in_scales[{p}]", t) for p, t in enumerate(in_scales)] + ([("out_scales", out_scales)] if out_scales is not None else [])
         for name, t in named:
             if t.dtype not in scale_types or not t.is_contiguous() or not t.is_cuda:
@@ -130,7 +138,7 @@ class HipEngine:
         ptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
         sptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in in_scales])
         _lib.call("fmi_dev_reduce_tree_mx", int(op), int(dtype), int(alg), int(_dtype(out)), out.data_ptr(),
-                  out_scales.data_ptr() if out_scales is not None else None, ptrs, sptrs, len(ins), rank, out.numel(),
+                  out_scales.data_ptr() if out_scales is not None else None, ptrs, sptrs, len(ins), rank, n,
                   self._stream())
 
     def fill_synthetic(self, t: torch.Tensor, seed: int, peer: int) -> None:

@@ -18,7 +18,8 @@ import numpy as np
 
 from ._lib import Timeout  # noqa: F401 - FMI_ERR_TIMEOUT, the reference's FMI::Utils::Timeout
 
-from .device import Alg, Bucket, DType, Op, _f32_word, _mx_elements, _mx_scales, _sptr, acc_dtype, dtype_of, itemsize_of
+from .device import (Alg, Bucket, DType, Op, _f32_word, _mx_elements, _mx_scales, _sptr, acc_dtype, dtype_of, itemsize_of,
+                     refuse_fp4)
 
 ID_BYTES = 128
 
@@ -122,6 +123,7 @@ class Comm:
         Op.AVG (float buckets; here, in allreduce_host and in reduce): the mean over the ranks, the sum's value times
         the rounded reciprocal of the rank count before the shard's one store (FMI_OP_AVG); Path.RCCL reduce-scatters
         with SUM and scales its shard. scan and reduce(sendbuf_partials=True) refuse it."""
+        refuse_fp4("allreduce", send, recv)
         alg = Alg.REDUCE_LTR if ordered else Alg.ALLREDUCE
         arg = acc_dtype(send.dtype, accumulate_f32)
         _lib.call("fmi_comm_allreduce", self.handle, int(op), arg, int(alg), int(path), _p(send), _p(recv), send.n,
@@ -148,7 +150,8 @@ class Comm:
         """The sharded allreduce of MX buckets (fmi_comm_allreduce_mx, path TREE): the sum (Op.SUM) or mean (Op.AVG)
         over the ranks of `send` under its block scales `send_scales` (F8E8M0, ceil(n / 32) bytes), in the reference's
         order, into `recv` on every rank: an F32 bucket (recv_scales None), or a bucket of send's dtype requantized
-        block by block with its scale bytes in `recv_scales`. The wire carries the element bytes and the scale bytes."""
+        block by block with its scale bytes in `recv_scales`. The wire carries the element bytes and the scale bytes.
+        F4E2M1 buckets (MXFP4) travel packed, at half the element bytes."""
         dtype = _mx_elements("allreduce_mx", "send bucket", send)
         if recv.n != send.n or recv.dtype not in (dtype, DType.F32):
             raise ValueError("allreduce_mx: `recv` must hold send's length in its dtype or in F32")
@@ -181,6 +184,8 @@ class Comm:
             raise ValueError("allreduce_host: arrays must share dtype and size")
         if not (send.flags.c_contiguous and recv.flags.c_contiguous):
             raise ValueError("allreduce_host: arrays must be contiguous")
+        if dtype is not None and DType(dtype) == DType.F4E2M1:
+            raise ValueError("allreduce_host: F4E2M1 is valid only in the MX calls")
         alg = Alg.REDUCE_LTR if ordered else Alg.ALLREDUCE
         arg = acc_dtype(dtype_of(send) if dtype is None else dtype, accumulate_f32)
         _lib.call("fmi_comm_allreduce_host", self.handle, int(op), arg, int(alg), int(path),
@@ -192,11 +197,13 @@ class Comm:
         forwarded up the binomial tree, reference src/comm/PeerToPeer.cpp:72) — fmi_comm_reduce_sendbuf."""
         alg = Alg.REDUCE_LTR if ordered else Alg.REDUCE
         fn = "fmi_comm_reduce_sendbuf" if sendbuf_partials else "fmi_comm_reduce"
+        refuse_fp4("reduce", send, recv)
         arg = acc_dtype(send.dtype, accumulate_f32)
         _lib.call(fn, self.handle, int(op), arg, int(alg), _p(send), _p(recv), send.n, root, _sptr(stream))
 
     def scan(self, op: Op, send: Bucket, recv: Bucket, ordered: bool = False, stream=None,
              accumulate_f32: bool = False) -> None:
+        refuse_fp4("scan", send, recv)
         alg = Alg.SCAN_LTR if ordered else Alg.SCAN
         arg = acc_dtype(send.dtype, accumulate_f32)
         _lib.call("fmi_comm_scan", self.handle, int(op), arg, int(alg), _p(send), _p(recv), send.n, _sptr(stream))

@@ -216,6 +216,42 @@ struct float8_e8m0 {
 inline bool operator==(float8_e8m0 a, float8_e8m0 b) { return a.bits == b.bits; }
 static_assert(sizeof(float8_e8m0) == 1 && std::is_trivially_copyable_v<float8_e8m0>, "a scale is its raw byte");
 
+// Two elements of an MXFP4 bucket (OCP E2M1: 1 sign, 2 exponent bits of bias 1, 1 mantissa bit; magnitudes 0, 0.5, 1, 1.5,
+// 2, 3, 4, 6; no inf, no NaN): element 2k in bits 3:0 of byte k, element 2k + 1 in bits 7:4. A byte type with no
+// arithmetic: only the MX calls below take buckets of it (FMI_F4E2M1 is valid nowhere else), with the ELEMENT count given
+// explicitly, since a bucket of n elements is (n + 1) / 2 bytes. widen / narrow are the library's definition of a
+// nibble's value on the host: narrow rounds to nearest with ties to the even code, keeps the sign, and is defined for
+// finite |f| <= 6 (what the scale rule at EMAX = 2 feeds it).
+struct float4_e2m1x2 {
+    std::uint8_t bits = 0;
+    float4_e2m1x2() = default;
+    static float4_e2m1x2 from_bits(std::uint8_t b) {
+        float4_e2m1x2 x;
+        x.bits = b;
+        return x;
+    }
+    static float4_e2m1x2 from_codes(std::uint8_t lo, std::uint8_t hi) { return from_bits(static_cast<std::uint8_t>((lo & 0xF) | (hi << 4))); }
+    std::uint8_t lo() const { return bits & 0xF; }
+    std::uint8_t hi() const { return bits >> 4; }
+    static float widen(std::uint8_t code) {
+        static constexpr float mag[8] = {0.0f, 0.5f, 1.0f, 1.5f, 2.0f, 3.0f, 4.0f, 6.0f};
+        return (code & 8) ? -mag[code & 7] : mag[code & 7];
+    }
+    static std::uint8_t narrow(float f) {
+        std::uint32_t u;
+        std::memcpy(&u, &f, sizeof u);
+        const std::uint32_t a = u & 0x7FFFFFFFu;
+        // the seven midpoints as float bits: one whose lower neighbour has the even code stays below (>), the others go up
+        const unsigned c = (a > 0x3E800000u) + (a >= 0x3F400000u) + (a > 0x3FA00000u) + (a >= 0x3FE00000u) + (a > 0x40200000u) +
+                           (a >= 0x40600000u) + (a > 0x40A00000u);
+        return static_cast<std::uint8_t>(c | ((u >> 28) & 8u));
+    }
+};
+inline bool operator==(float4_e2m1x2 a, float4_e2m1x2 b) { return a.bits == b.bits; }
+static_assert(sizeof(float4_e2m1x2) == 1 && std::is_trivially_copyable_v<float4_e2m1x2>, "two E2M1 elements are one raw byte");
+// The bytes of an MXFP4 bucket of n elements.
+inline std::size_t fp4_bytes(std::size_t n) { return (n + 1) / 2; }
+
 // The float element types narrower than float: their values are held and scaled (the mean) in float.
 template <class A>
 inline constexpr bool narrow_float_v = std::is_same_v<A, half> || std::is_same_v<A, bfloat16> ||
@@ -248,9 +284,10 @@ constexpr int dtype_of() {
 
 template <class A>
 constexpr bool device_type = dtype_of<A>() >= 0;
-// What a Bucket can hold: the device element types, and the scale bytes of MX buckets, which only the MX calls take.
+// What a Bucket can hold: the device element types, and the scale bytes of MX buckets and the packed bytes of MXFP4
+// buckets, which only the MX calls take.
 template <class A>
-constexpr bool bucket_storage = device_type<A> || std::is_same_v<A, float8_e8m0>;
+constexpr bool bucket_storage = device_type<A> || std::is_same_v<A, float8_e8m0> || std::is_same_v<A, float4_e2m1x2>;
 
 // Select the device for this process (one process per GPU, as FMI runs one peer per process).
 inline void init(int device = 0) { check(fmi_dev_init(device), "fmi_dev_init"); }
@@ -265,7 +302,7 @@ inline void sync() { check(fmi_dev_sync(), "fmi_dev_sync"); }
 // A device-resident bucket of n elements of A (owning, move-only).
 template <class A>
 class Bucket {
-    static_assert(bucket_storage<A>, "device buckets hold float, double, Dev::half, Dev::bfloat16, Dev::float8_e4m3, Dev::float8_e5m2, 8/16/32/64-bit integers or Dev::float8_e8m0 scale bytes");
+    static_assert(bucket_storage<A>, "device buckets hold float, double, Dev::half, Dev::bfloat16, Dev::float8_e4m3, Dev::float8_e5m2, 8/16/32/64-bit integers, Dev::float8_e8m0 scale bytes or Dev::float4_e2m1x2 bytes");
 
 public:
     using value_type = A;
@@ -439,6 +476,54 @@ inline void mx_dequantize(Bucket<D>& dst, const Bucket<A>& src, const Bucket<flo
     static_assert(std::is_same_v<D, float> || std::is_same_v<D, half> || std::is_same_v<D, bfloat16>, "mx_dequantize: float, Dev::half or Dev::bfloat16 destination");
     if (dst.size() != src.size() || src_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_dequantize: size mismatch");
     check(fmi_dev_mx_dequantize(dtype_of<D>(), dst.data(), dtype_of<A>(), src.data(), src_scales.data(), src.size(), stream), "fmi_dev_mx_dequantize");
+}
+
+// MXFP4 (fmi_dev_reduce_tree_mx at FMI_F4E2M1): buckets of Dev::float4_e2m1x2 bytes, fp4_bytes(n) of them for n
+// ELEMENTS, which every call takes explicitly or from its float side; scale bytes as above, EMAX = 2 in the scale rule.
+namespace detail {
+inline void reduce_tree_mxfp4(int op, int alg, int out_dtype, void* out, void* out_scales, std::size_t n,
+                              const std::vector<const Bucket<float4_e2m1x2>*>& ins,
+                              const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank, fmi_stream_t stream) {
+    if (ins.empty() || ins.size() > static_cast<std::size_t>(std::numeric_limits<int>::max()) || in_scales.size() != ins.size())
+        throw std::runtime_error("Dev::reduce_tree_mx: need at least one input bucket and one scale bucket per input");
+    std::vector<const void*> ptrs, sptrs;
+    for (std::size_t p = 0; p < ins.size(); ++p) {
+        if (!ins[p] || ins[p]->size() != fp4_bytes(n)) throw std::runtime_error("Dev::reduce_tree_mx: an MXFP4 bucket of n elements holds (n + 1) / 2 bytes");
+        if (!in_scales[p] || in_scales[p]->size() != mx_blocks(n))
+            throw std::runtime_error("Dev::reduce_tree_mx: a scale bucket holds (n + 31) / 32 bytes");
+        ptrs.push_back(ins[p]->data());
+        sptrs.push_back(in_scales[p]->data());
+    }
+    check(fmi_dev_reduce_tree_mx(op, FMI_F4E2M1, alg, out_dtype, out, out_scales, ptrs.data(), sptrs.data(),
+                                 static_cast<int>(ins.size()), rank, n, stream),
+          "fmi_dev_reduce_tree_mx");
+}
+}  // namespace detail
+
+inline void reduce_tree_mx(int op, int alg, Bucket<float4_e2m1x2>& out, Bucket<float8_e8m0>& out_scales, std::size_t n,
+                           const std::vector<const Bucket<float4_e2m1x2>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank = 0, fmi_stream_t stream = nullptr) {
+    if (out.size() != fp4_bytes(n) || out_scales.size() != mx_blocks(n))
+        throw std::runtime_error("Dev::reduce_tree_mx: out holds (n + 1) / 2 bytes and out_scales (n + 31) / 32");
+    detail::reduce_tree_mxfp4(op, alg, FMI_F4E2M1, out.data(), out_scales.data(), n, ins, in_scales, rank, stream);
+}
+inline void reduce_tree_mx(int op, int alg, Bucket<float>& out, std::size_t n, const std::vector<const Bucket<float4_e2m1x2>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank = 0, fmi_stream_t stream = nullptr) {
+    if (out.size() != n) throw std::runtime_error("Dev::reduce_tree_mx: a float output holds n elements");
+    detail::reduce_tree_mxfp4(op, alg, FMI_F32, out.data(), nullptr, n, ins, in_scales, rank, stream);
+}
+// n is the float side's length.
+template <class S>
+inline void mx_quantize(Bucket<float4_e2m1x2>& out, Bucket<float8_e8m0>& out_scales, const Bucket<S>& src, fmi_stream_t stream = nullptr) {
+    static_assert(std::is_same_v<S, float> || std::is_same_v<S, half> || std::is_same_v<S, bfloat16>, "mx_quantize: float, Dev::half or Dev::bfloat16 source");
+    if (out.size() != fp4_bytes(src.size()) || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
+    check(fmi_dev_mx_quantize(FMI_F4E2M1, out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), stream), "fmi_dev_mx_quantize");
+}
+template <class D>
+inline void mx_dequantize(Bucket<D>& dst, const Bucket<float4_e2m1x2>& src, const Bucket<float8_e8m0>& src_scales, fmi_stream_t stream = nullptr) {
+    static_assert(std::is_same_v<D, float> || std::is_same_v<D, half> || std::is_same_v<D, bfloat16>, "mx_dequantize: float, Dev::half or Dev::bfloat16 destination");
+    if (src.size() != fp4_bytes(dst.size()) || src_scales.size() != mx_blocks(dst.size())) throw std::runtime_error("Dev::mx_dequantize: size mismatch");
+    check(fmi_dev_mx_dequantize(dtype_of<D>(), dst.data(), FMI_F4E2M1, src.data(), src_scales.data(), dst.size(), stream), "fmi_dev_mx_dequantize");
 }
 
 // Untyped device scratch used by the channel algorithms for temporaries of device-resident buckets.

@@ -1458,6 +1458,7 @@ int check_common(fmi_comm_t comm, int op, int* dtype, int* kd, const char* who =
     if (op != FMI_OP_AVG && (op < FMI_OP_SUM || op > FMI_OP_MIN)) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
     FMI_COMM_RC(canonical_dtype(op, *dtype, true, 0, kd));
     *dtype = storage_dtype(*kd);
+    if (int rc = refuse_fp4(*dtype)) return rc;
     if (dtype_size(*dtype) == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(*dtype));
     if (op == FMI_OP_AVG && !is_float(*dtype))
         return refuse_avg(op, "fmi_comm", ("dtype " + std::to_string(*dtype) + " is an integer dtype").c_str());
@@ -1791,13 +1792,18 @@ int allreduce_mx_device(Comm* c, int op, int dtype, int alg, int out_dtype, cons
     const int N = c->t->n();
     if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE))  // the P = 1 form: not a copy
         return reduce_tree_mx(op, dtype, alg, out_dtype, recv, recv_scales, &send, &send_scales, 1, 0, n, s);
-    static_assert(kShardAlign % 32 == 0, "shard boundaries are MX block boundaries");
+    static_assert(kShardAlign % 32 == 0, "shard boundaries are MX block (and so FP4 byte) boundaries");
     const bool wide = out_dtype == FMI_F32;
-    const size_t osz = dtype_size(out_dtype);  // the inputs' element size is 1
-    const size_t shard = shard_elems(n, N), padded = shard * N;
+    // Byte counts: eb per input shard (shard for the 8-bit floats; shard / 2 for FMI_F4E2M1, whole bytes and whole
+    // blocks because kShardAlign is even), ob per output shard, nb / nob for the buckets' first n elements. Only the last
+    // non-empty shard can have an odd TRUE length, and its kernel writes that byte's high nibble as 0.
+    const size_t shard = shard_elems(n, N);
+    const size_t eb = mx_elem_bytes(dtype, shard), ob = wide ? shard * sizeof(float) : eb;
+    const size_t nb = mx_elem_bytes(dtype, n), nob = wide ? n * sizeof(float) : nb;
+    const bool ragged = shard * N != n;
     const size_t nsc = (n + 31) / 32, sshard = shard / 32, spadded = sshard * N;
     const char* src = nullptr;
-    FMI_COMM_RC(padded_source(c, n, padded, 1, send, s, &src));
+    FMI_COMM_RC(padded_source(c, nb, eb * N, 1, send, s, &src));
     const char* ssrc = static_cast<const char*>(send_scales);
     if (spadded != nsc) {
         char* pad = nullptr;
@@ -1807,27 +1813,27 @@ int allreduce_mx_device(Comm* c, int op, int dtype, int alg, int out_dtype, cons
         ssrc = pad;
     }
     char *staging = nullptr, *red = nullptr, *sstaging = nullptr, *sred = nullptr;
-    FMI_COMM_RC(c->scratch(1, padded, s, &staging));
-    FMI_COMM_RC(c->scratch(2, shard * osz, s, &red));
+    FMI_COMM_RC(c->scratch(1, eb * N, s, &staging));
+    FMI_COMM_RC(c->scratch(2, ob, s, &red));
     FMI_COMM_RC(c->scratch(20, spadded, s, &sstaging));
     FMI_COMM_RC(c->scratch(21, sshard, s, &sred));
-    FMI_COMM_RC(c->t->all_to_all(src, staging, shard, s));
+    FMI_COMM_RC(c->t->all_to_all(src, staging, eb, s));
     FMI_COMM_RC(c->t->all_to_all(ssrc, sstaging, sshard, s));
     const size_t len = Transport::span(c->t->rank(), shard, n);  // elements of my shard
     if (len) {
         std::vector<const void*> parts(N), sparts(N);
-        for (int j = 0; j < N; ++j) parts[j] = staging + j * shard, sparts[j] = sstaging + j * sshard;
+        for (int j = 0; j < N; ++j) parts[j] = staging + j * eb, sparts[j] = sstaging + j * sshard;
         FMI_COMM_RC(c->timing.begin(s));
         FMI_COMM_RC(reduce_tree_mx(op, dtype, alg, out_dtype, red, sred, parts.data(), sparts.data(), N, 0, len, s));
         FMI_COMM_RC(c->timing.end(s));
     }
-    if (padded == n) {
-        FMI_COMM_RC(c->t->all_gather(red, static_cast<char*>(recv), shard * osz, s));
+    if (!ragged) {
+        FMI_COMM_RC(c->t->all_gather(red, static_cast<char*>(recv), ob, s));
     } else {
         char* out = nullptr;
-        FMI_COMM_RC(c->scratch(3, padded * osz, s, &out));
-        FMI_COMM_RC(c->t->all_gather(red, out, shard * osz, s));
-        FMI_COMM_RC(device_copy(recv, out, n * osz, s));
+        FMI_COMM_RC(c->scratch(3, ob * N, s, &out));
+        FMI_COMM_RC(c->t->all_gather(red, out, ob, s));
+        FMI_COMM_RC(device_copy(recv, out, nob, s));
     }
     if (wide) return FMI_OK;
     if (spadded == nsc) {

@@ -769,12 +769,17 @@ int run_scan_blocked(int op, int dtype, int alg, void* const* outs, const void* 
     return rc;
 }
 
-int check_peer_args(int op, int dtype, int P) {
-    if (op < FMI_OP_SUM || op > FMI_OP_MIN) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
-    if (dtype_size(dtype) == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(dtype));
+int check_peer_count(int P) {
     if (P < 1 || P > sched::kMaxPeers)
         return fail(FMI_ERR_INVALID, "P must be in [1, " + std::to_string(sched::kMaxPeers) + "], got " + std::to_string(P));
     return FMI_OK;
+}
+
+int check_peer_args(int op, int dtype, int P) {
+    if (op < FMI_OP_SUM || op > FMI_OP_MIN) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
+    if (int rc = refuse_fp4(dtype)) return rc;
+    if (dtype_size(dtype) == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(dtype));
+    return check_peer_count(P);
 }
 
 // Symbolic evaluation of a program, for fmi_schedule_expr.
@@ -1617,6 +1622,7 @@ int fmi_host_reduce_pair(int op, int dtype, void* inout, const void* in, size_t 
 
 int fmi_dev_fill_synthetic_at(int dtype, void* buf, size_t n, uint64_t seed, uint32_t peer, uint64_t first,
                               fmi_stream_t stream) {
+    if (int rc = refuse_fp4(dtype)) return rc;
     if (n == 0) return FMI_OK;
     if (!buf) return fail(FMI_ERR_INVALID, "null buffer");
     if (int rc = require_device()) return rc;
@@ -1656,6 +1662,7 @@ int fmi_dev_reduce_tree(int op, int dtype, int alg, void* out, const void* const
 
 int fmi_dev_mean_scale(int dtype, void* inout, size_t n, int P, fmi_stream_t stream) {
     return guarded("fmi_dev_mean_scale", [&]() -> int {
+        if (int rc = refuse_fp4(dtype)) return rc;
         if (dtype_size(dtype) == 0) return fail(FMI_ERR_INVALID, "fmi_dev_mean_scale: unknown dtype " + std::to_string(dtype));
         if (!is_float(dtype))
             return fail(FMI_ERR_INVALID, "fmi_dev_mean_scale: dtype " + std::to_string(dtype) + " is an integer dtype; the mean "
@@ -1670,10 +1677,12 @@ int fmi_dev_mean_scale(int dtype, void* inout, size_t n, int P, fmi_stream_t str
 
 int fmi_dev_convert(int dst_dtype, void* dst, int src_dtype, const void* src, size_t n, fmi_stream_t stream) {
     return guarded("fmi_dev_convert", [&]() -> int {
-        for (const int d : {dst_dtype, src_dtype})
+        for (const int d : {dst_dtype, src_dtype}) {
+            if (int rc = refuse_fp4(d)) return rc;
             if (d != FMI_F32 && !is_half_dtype(d) && !is_fp8_dtype(d))
                 return fail(FMI_ERR_INVALID, "fmi_dev_convert: dtype " + std::to_string(d) + " is not one of FMI_F32, FMI_F16, "
                                              "FMI_BF16, FMI_F8E4M3, FMI_F8E5M2 (FMI_ACC_F32 is not valid here)");
+        }
         if (n == 0) return FMI_OK;
         if (!dst || !src) return fail(FMI_ERR_INVALID, "null buffer");
         if (int rc = require_device()) return rc;
@@ -1767,6 +1776,7 @@ int scaled_check_args(const char* who, int op, int dtype_arg, int alg, int out_d
         return fail(FMI_ERR_INVALID, w + "op " + std::to_string(op) + " is not valid here: only FMI_OP_SUM is a scaled reduction "
                                          "(PROD / MAX / MIN are out of scope)");
     *dtype = storage_dtype(dtype_arg);
+    if (int rc = refuse_fp4(dtype_arg)) return rc;
     if (!is_fp8_dtype(*dtype))
         return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype_arg) + " is not FMI_F8E4M3 or FMI_F8E5M2, the storage "
                                          "types a scaled bucket can have");
@@ -1849,9 +1859,9 @@ int mx_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype
         return fail(FMI_ERR_INVALID, w + "op " + std::to_string(op) + " is not valid here: an MX reduction is FMI_OP_SUM or "
                                          "FMI_OP_AVG (PROD / MAX / MIN are out of scope)");
     *dtype = storage_dtype(dtype_arg);
-    if (!is_fp8_dtype(*dtype))
-        return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype_arg) + " is not FMI_F8E4M3 or FMI_F8E5M2, the element "
-                                         "types an MX bucket can have");
+    if (!is_mx_dtype(*dtype))
+        return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype_arg) + " is not FMI_F8E4M3 or FMI_F8E5M2 (MXFP8) or "
+                                         "FMI_F4E2M1 (MXFP4), the element types an MX bucket can have");
     if (alg == FMI_ALG_SCAN || alg == FMI_ALG_SCAN_LTR)
         return fail(FMI_ERR_INVALID, w + "alg " + std::to_string(alg) + " is a scan algorithm; an MX reduction takes "
                                          "FMI_ALG_ALLREDUCE, FMI_ALG_REDUCE or FMI_ALG_REDUCE_LTR");
@@ -1869,9 +1879,9 @@ int mx_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype
 // dtype: FMI_F8E4M3 / FMI_F8E5M2; wide: the other side's dtype, named `what` in the message.
 static int mx_check_convert(const char* who, int dtype, const char* what, int wide) {
     const std::string w = std::string(who) + ": ";
-    if (!is_fp8_dtype(dtype))
-        return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype) + " is not FMI_F8E4M3 or FMI_F8E5M2, the element "
-                                         "types an MX bucket can have");
+    if (!is_mx_dtype(dtype))
+        return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype) + " is not FMI_F8E4M3 or FMI_F8E5M2 (MXFP8) or "
+                                         "FMI_F4E2M1 (MXFP4), the element types an MX bucket can have");
     if (wide != FMI_F32 && wide != FMI_F16 && wide != FMI_BF16)
         return fail(FMI_ERR_INVALID, w + what + " " + std::to_string(wide) + " must be FMI_F32, FMI_F16 or FMI_BF16");
     return FMI_OK;
@@ -1932,7 +1942,7 @@ int fmi_dev_reduce_tree_mx(int op, int dtype_arg, int alg, int out_dtype, void* 
     return guarded("fmi_dev_reduce_tree_mx", [&]() -> int {
         int dtype = 0;
         if (int rc = mx_check_args("fmi_dev_reduce_tree_mx", op, dtype_arg, alg, out_dtype, out_scales, &dtype)) return rc;
-        if (int rc = check_peer_args(FMI_OP_SUM, dtype, P)) return rc;
+        if (int rc = check_peer_count(P)) return rc;  // op and dtype: mx_check_args above
         if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
         if (!out || !ins || !in_scales) return fail(FMI_ERR_INVALID, "null buffer");
         for (int p = 0; p < P; ++p)

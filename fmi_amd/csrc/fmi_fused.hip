@@ -14,6 +14,8 @@
 //                            floats, 8-bit and f32 output; their own entry, launch_fused_scaled below)
 //   MX 8-bit sums and means  fmi_fused_mx_*.hip, one per reduce algorithm (fmi_dev_reduce_tree_mx: both 8-bit floats, 8-bit
 //                            and f32 output; their own entry, launch_fused_mx below)
+//   MXFP4 sums and means     fmi_fused_mxfp4_*.hip, one per reduce algorithm (the same call at FMI_F4E2M1: E2M1 and f32
+//                            output; launch_fused_mx too)
 // Everything else a call can be runs elsewhere (fmi_dev.hip): P beyond a variant's kernels and unaligned buckets as
 // blocks of fused programs, as widen / the f32 program / narrow, as the SUM program and the scale kernel
 // (fmi_scale.hip), or as pairwise passes in the program's order.
@@ -135,6 +137,14 @@ int launch_fused_scaled(int alg, int dtype, int out_dtype, int P, const PeerPtrs
 }
 
 int launch_fused_mx(int alg, int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s) {
+    if (dtype == FMI_F4E2M1) {  // MXFP4: fmi_fused_mxfp4_*.hip
+        switch (alg) {
+            case sched::kAllreduce: return mxfp4_unit<sched::kAllreduce>(out_dtype, P, ptrs, mx, n, s);
+            case sched::kReduce: return mxfp4_unit<sched::kReduce>(out_dtype, P, ptrs, mx, n, s);
+            case sched::kReduceLtr: return mxfp4_unit<sched::kReduceLtr>(out_dtype, P, ptrs, mx, n, s);
+            default: return fail(FMI_ERR_INVALID, "fused MXFP4 launch: no kernel for algorithm " + std::to_string(alg));
+        }
+    }
     switch (alg) {
         case sched::kAllreduce: return mx_unit<sched::kAllreduce>(dtype, out_dtype, P, ptrs, mx, n, s);
         case sched::kReduce: return mx_unit<sched::kReduce>(dtype, out_dtype, P, ptrs, mx, n, s);

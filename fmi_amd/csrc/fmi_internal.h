@@ -50,6 +50,16 @@ inline bool is_half_dtype(int dtype) { return dtype == FMI_F16 || dtype == FMI_B
 // The 8-bit float dtypes: the pairwise family, and with FMI_ACC_F32 the fused kernels of fmi_fused_fp8_acc32_*.hip.
 // Their plain P-way programs have no fused kernel (out of scope on purpose): they run as pairwise passes in order.
 inline bool is_fp8_dtype(int dtype) { return dtype == FMI_F8E4M3 || dtype == FMI_F8E5M2; }
+// The element types an MX bucket can have: the two 8-bit floats and FMI_F4E2M1, which is valid in the MX calls ALONE
+// (two elements to a byte: mx_elem_bytes). Every other entry point refuses it on the host, naming it (refuse_fp4).
+inline bool is_mx_dtype(int dtype) { return is_fp8_dtype(dtype) || dtype == FMI_F4E2M1; }
+inline size_t mx_elem_bytes(int dtype, size_t n) { return dtype == FMI_F4E2M1 ? n / 2 + n % 2 : n; }
+inline int refuse_fp4(int dtype_arg) {
+    if ((dtype_arg & ~FMI_ACC_F32) != FMI_F4E2M1) return FMI_OK;  // with or without the flag
+    return fail(FMI_ERR_INVALID, "dtype " + std::to_string(dtype_arg) + " (FMI_F4E2M1) is valid only as the element type of "
+                                 "the MX calls (fmi_dev_reduce_tree_mx, fmi_dev_mx_quantize, fmi_dev_mx_dequantize, "
+                                 "fmi_comm_allreduce_mx): 4-bit elements have no other kernel");
+}
 
 // The dtype ARGUMENT of a P-way call may carry FMI_ACC_F32 (include/fmi_dev.h): its storage dtype, which sizes,
 // alignment, order_sensitive, fused_covers and with_dtype take, and whether the program's values are kept in f32.
@@ -61,6 +71,7 @@ inline bool accumulates_f32(int dtype_arg) { return (dtype_arg & FMI_ACC_F32) !=
 // dtype, with the flag where the call accumulates in f32. An unknown storage dtype is left to the caller's own check.
 inline int canonical_dtype(int op, int dtype_arg, bool pway, int P, int* canon) {
     *canon = storage_dtype(dtype_arg);
+    if (int rc = refuse_fp4(dtype_arg)) return rc;
     if (!accumulates_f32(dtype_arg)) return FMI_OK;
     if (!is_half_dtype(*canon) && !is_fp8_dtype(*canon))
         return fail(FMI_ERR_INVALID, "dtype " + std::to_string(dtype_arg) + ": FMI_ACC_F32 is valid only as FMI_F16 | FMI_ACC_F32, "
@@ -151,6 +162,7 @@ int with_dtype(int dtype, F&& f) {
             default: break;
         }
     }
+    if (int rc = refuse_fp4(dtype)) return rc;
     return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(dtype));
 }
 
@@ -257,8 +269,13 @@ int launch_fused_mx(int alg, int dtype, int out_dtype, int P, const PeerPtrs& pt
 using MxUnit = int(int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
 template <int ALG>
 MxUnit mx_unit;
-// fmi_dev_mx_dequantize / fmi_dev_mx_quantize (fmi_mx.hip), any alignment, one launch each. dtype: FMI_F8E4M3 /
-// FMI_F8E5M2; dst_dtype / src_dtype: FMI_F32, FMI_F16 or FMI_BF16 (FMI_ERR_INVALID otherwise).
+// The MXFP4 kernels of one algorithm (dtype FMI_F4E2M1, P = 2..16, both outputs; n counts elements, two to a byte):
+// defined in fmi_mxfp4_impl.h, instantiated by one fmi_fused_mxfp4_*.hip each. launch_fused_mx sends dtype FMI_F4E2M1 here.
+using Mxfp4Unit = int(int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
+template <int ALG>
+Mxfp4Unit mxfp4_unit;
+// fmi_dev_mx_dequantize / fmi_dev_mx_quantize (fmi_mx.hip), any alignment, one launch each. dtype: FMI_F8E4M3,
+// FMI_F8E5M2 or FMI_F4E2M1 (packed: n elements in ceil(n / 2) bytes); dst_dtype / src_dtype: FMI_F32, FMI_F16 or FMI_BF16 (FMI_ERR_INVALID otherwise).
 int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s);
 int launch_mx_quantize(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s);
 // The host-side checks of fmi_dev_reduce_tree_mx's op, dtype argument, alg, out_dtype and out_scales (fmi_dev.hip),

@@ -6,7 +6,10 @@
 // Any alignment: one element per thread and step, grid-stride; a block of 32 elements is one half of a wave, so its
 // amax is five shuffles inside the half. The waves' loops are uniform (a wave leaves only when all its elements are
 // beyond n), so every shuffle has all its lanes. These are the fallback's passes, not a hot path.
-#include "fmi_mx_impl.h"
+// FMI_F4E2M1 (two elements to a byte): one BYTE per thread and step, so nothing needs sub-byte addressing or atomics;
+// a block of 32 elements is 16 threads, a quarter of a wave, and its amax four shuffles inside the quarter. Table
+// widening and the integer-code narrowing of fmi_mxfp4_impl.h.
+#include "fmi_mxfp4_impl.h"
 
 namespace fmi::dev {
 namespace {
@@ -51,6 +54,53 @@ __global__ void __launch_bounds__(kBlock) mx_quantize_kernel(T* out, uint8_t* ou
     }
 }
 
+// n: elements; the bucket is n / 2 + n % 2 bytes, and the last byte's high nibble is not an element when n is odd.
+template <class D>
+__global__ void __launch_bounds__(kBlock) mxfp4_dequantize_kernel(D* dst, const uint8_t* src, const uint8_t* scales, size_t n) {
+    const size_t nbytes = n / 2 + n % 2;
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < nbytes; i += stride) {
+        const uint32_t b = src[i];
+        const float sc = mx_scale32(scales[i / 16]);
+        Lanes<float, 1> v;
+        v.v[0] = fp4_widen_sw(b) * sc;
+        dst[2 * i] = to_storage<D>(v).v[0];
+        if (2 * i + 1 < n) {
+            v.v[0] = fp4_widen_sw(b >> 4) * sc;
+            dst[2 * i + 1] = to_storage<D>(v).v[0];
+        }
+    }
+}
+
+template <class S>
+__global__ void __launch_bounds__(kBlock) mxfp4_quantize_kernel(uint8_t* out, uint8_t* out_scales, const S* src, size_t n) {
+    const size_t nbytes = n / 2 + n % 2;
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    const unsigned lane = threadIdx.x % 64;
+    // `wave0`: the first byte of this wave's 64 (four blocks); the loop's condition is the wave's, not the lane's
+    for (size_t wave0 = static_cast<size_t>(blockIdx.x) * blockDim.x + (threadIdx.x - lane); wave0 < nbytes; wave0 += stride) {
+        const size_t i = wave0 + lane;
+        float x[2] = {0.0f, 0.0f};  // beyond the bucket: +0, whose code 0 is what an odd bucket's last high nibble takes
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (2 * i + k < n) {
+                Lanes<S, 1> raw;
+                raw.v[0] = src[2 * i + k];
+                x[k] = to_value<float>(raw).v[0];
+            }
+        uint32_t A = max(mx_abs_bits(x[0]), mx_abs_bits(x[1]));
+#pragma unroll
+        for (int d = 8; d > 0; d >>= 1) A = max(A, static_cast<uint32_t>(__shfl_xor(static_cast<int>(A), d, 64)));
+        const uint32_t e_out = mxfp4_scale_byte(A);
+        const float inv = mx_inv_scale(e_out);
+        if (i < nbytes) {
+            const uint32_t b = e_out == 255u ? 0u : fp4_narrow_sw(x[0] * inv) | (fp4_narrow_sw(x[1] * inv) << 4);
+            out[i] = static_cast<uint8_t>(b);
+            if (lane % 16 == 0) out_scales[i / 16] = static_cast<uint8_t>(e_out);
+        }
+    }
+}
+
 unsigned grid_of(size_t n) { return static_cast<unsigned>(std::min(grid_for(n, kBlock), kGridCap)); }
 
 // f.template operator()<D>() for the non-MX side of a conversion: FMI_F32, FMI_F16 or FMI_BF16.
@@ -69,6 +119,11 @@ int with_wide_dtype(const char* who, const char* what, int dtype, F&& f) {
 
 int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s) {
     if (n == 0) return FMI_OK;
+    if (dtype == FMI_F4E2M1)
+        return with_wide_dtype("fmi_dev_mx_dequantize", "dst_dtype", dst_dtype, [&]<class D>() -> int {
+            mxfp4_dequantize_kernel<D><<<grid_of(n / 2 + n % 2), kBlock, 0, s>>>(static_cast<D*>(dst), static_cast<const uint8_t*>(src), scales, n);
+            return check_launch("MXFP4 dequantize kernel launch");
+        });
     return with_dtype<kTierFp8>(dtype, [&]<class T>() -> int {
         return with_wide_dtype("fmi_dev_mx_dequantize", "dst_dtype", dst_dtype, [&]<class D>() -> int {
             mx_dequantize_kernel<T, D><<<grid_of(n), kBlock, 0, s>>>(static_cast<D*>(dst), static_cast<const T*>(src), scales, n);
@@ -79,6 +134,11 @@ int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, c
 
 int launch_mx_quantize(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s) {
     if (n == 0) return FMI_OK;
+    if (dtype == FMI_F4E2M1)
+        return with_wide_dtype("fmi_dev_mx_quantize", "src_dtype", src_dtype, [&]<class S>() -> int {
+            mxfp4_quantize_kernel<S><<<grid_of(n / 2 + n % 2), kBlock, 0, s>>>(static_cast<uint8_t*>(out), out_scales, static_cast<const S*>(src), n);
+            return check_launch("MXFP4 quantize kernel launch");
+        });
     return with_dtype<kTierFp8>(dtype, [&]<class T>() -> int {
         return with_wide_dtype("fmi_dev_mx_quantize", "src_dtype", src_dtype, [&]<class S>() -> int {
             mx_quantize_kernel<T, S><<<grid_of(n), kBlock, 0, s>>>(static_cast<T*>(out), out_scales, static_cast<const S*>(src), n);

@@ -52,6 +52,10 @@ class DType(enum.IntEnum):
     # The scale bytes of an MX bucket (E8M0: 2^(e - 127), 255 = NaN), one per 32 elements, over np.uint8. A label of this
     # binding alone (include/fmi_dev.h reserves the value): no C-ABI call takes it as an element dtype.
     F8E8M0 = 14
+    # The OCP 4-bit float E2M1, the element of an MXFP4 bucket: two elements to a byte over np.uint8 (element 2k in bits
+    # 3:0 of byte k, element 2k + 1 in bits 7:4), so a Bucket of n ELEMENTS holds (n + 1) // 2 bytes. Valid in the MX
+    # calls alone (reduce_tree_mx, mx_quantize, mx_dequantize, Comm.allreduce_mx): every other call raises ValueError.
+    F4E2M1 = 15
 
 
 # fmi_dev.h's FMI_ACC_F32: ORed into the dtype argument of a P-way call on F16 / BF16 / F8E4M3 / F8E5M2 buckets, the program's values
@@ -101,7 +105,45 @@ NP_DTYPE = {DType.F32: np.float32, DType.F64: np.float64, DType.I32: np.int32, D
             DType.U16: np.uint16, DType.F16: np.float16}
 # numpy has no bfloat16 and no 8-bit floats: a BF16 bucket moves its elements' raw bits as np.uint16, an F8E4M3 /
 # F8E5M2 bucket as np.uint8 (np.uint8 alone keeps meaning U8)
-_HOST_DTYPE = {**NP_DTYPE, DType.BF16: np.uint16, DType.F8E4M3: np.uint8, DType.F8E5M2: np.uint8, DType.F8E8M0: np.uint8}
+_HOST_DTYPE = {**NP_DTYPE, DType.BF16: np.uint16, DType.F8E4M3: np.uint8, DType.F8E5M2: np.uint8, DType.F8E8M0: np.uint8,
+               DType.F4E2M1: np.uint8}
+
+
+def storage_bytes(dtype: "DType", n: int) -> int:
+    """The bytes a bucket of n elements takes: n times the element size, or (n + 1) // 2 for the packed F4E2M1."""
+    if dtype == DType.F4E2M1:
+        return (int(n) + 1) // 2
+    return int(n) * np.dtype(_HOST_DTYPE[dtype]).itemsize
+
+
+def refuse_fp4(who: str, *buckets) -> None:
+    """F4E2M1 buckets are valid in the MX calls alone: every other call refuses them before it reaches the library."""
+    for b in buckets:
+        if getattr(b, "dtype", None) == DType.F4E2M1:
+            raise ValueError(f"{who}: F4E2M1 buckets are valid only in reduce_tree_mx, mx_quantize, mx_dequantize and "
+                             f"Comm.allreduce_mx")
+
+
+def fp4_pack(nibbles) -> np.ndarray:
+    """E2M1 codes (one per element, 0..15) packed two to a byte: element 2k in bits 3:0 of byte k, element 2k + 1 in bits
+    7:4; an odd count leaves the last byte's high nibble 0."""
+    c = np.ascontiguousarray(nibbles, dtype=np.uint8).ravel()
+    if c.size and int(c.max()) > 15:
+        raise ValueError("fp4_pack: codes must be in 0..15")
+    if c.size % 2:
+        c = np.concatenate([c, np.zeros(1, np.uint8)])
+    return (c[0::2] | (c[1::2] << 4)).astype(np.uint8)
+
+
+def fp4_unpack(packed, n: int) -> np.ndarray:
+    """The n E2M1 codes of a packed bucket ((n + 1) // 2 bytes): the inverse of fp4_pack."""
+    b = np.ascontiguousarray(packed, dtype=np.uint8).ravel()
+    if b.size != (int(n) + 1) // 2:
+        raise ValueError(f"fp4_unpack: {n} elements are {(int(n) + 1) // 2} bytes, got {b.size}")
+    out = np.empty(2 * b.size, np.uint8)
+    out[0::2] = b & 0xF
+    out[1::2] = b >> 4
+    return out[:int(n)]
 
 
 def dtype_of(arr_or_dtype) -> DType:
@@ -194,7 +236,7 @@ class Bucket:
 
     @property
     def nbytes(self) -> int:
-        return self.n * self.itemsize
+        return storage_bytes(self.dtype, self.n)
 
     @classmethod
     def group(cls, count: int, n: int, dtype) -> list:
@@ -202,7 +244,7 @@ class Bucket:
         operands): fmi_dev_alloc_group puts bucket j in 4 KiB slot j mod 16, whatever was allocated before
         (DESIGN §4)."""
         dt = dtype_of(dtype) if not isinstance(dtype, DType) else dtype
-        nbytes = int(n) * np.dtype(_HOST_DTYPE[dt]).itemsize
+        nbytes = storage_bytes(dt, n)
         ptrs = (ctypes.c_void_p * max(int(count), 1))()
         _lib.call("fmi_dev_alloc_group", ptrs, int(count), nbytes)
         out = []
@@ -220,26 +262,32 @@ class Bucket:
         return b
 
     def view(self, offset: int, n: int) -> "Bucket":
-        """Sub-bucket starting `offset` elements in (used to exercise unaligned buckets)."""
+        """Sub-bucket starting `offset` elements in (used to exercise unaligned buckets). An F4E2M1 bucket needs an even
+        element offset: a view starts on a byte."""
         if offset < 0 or offset + n > self.n:
             raise ValueError("view out of range")
+        if self.dtype == DType.F4E2M1:
+            if offset % 2:
+                raise ValueError("view: an F4E2M1 bucket needs an even element offset (two elements to a byte)")
+            return Bucket(n, self.dtype, ptr=self.ptr + offset // 2, owner=self)
         return Bucket(n, self.dtype, ptr=self.ptr + offset * self.itemsize, owner=self)
 
     def upload(self, arr: np.ndarray, stream=None) -> None:
         arr = np.ascontiguousarray(arr, dtype=_HOST_DTYPE[self.dtype])
-        if arr.size != self.n:
+        if arr.nbytes != self.nbytes:  # F4E2M1: the packed bytes, (n + 1) // 2 of them
             raise ValueError(f"size mismatch: bucket has {self.n} elements, array {arr.size}")
         _lib.call("fmi_dev_h2d_async", self.ptr, arr.ctypes.data, self.nbytes, _sptr(stream))
         _lib.call("fmi_stream_sync", _sptr(stream))
 
     def numpy(self, stream=None) -> np.ndarray:
-        out = np.empty(self.n, dtype=_HOST_DTYPE[self.dtype])
+        out = np.empty(self.nbytes // self.itemsize, dtype=_HOST_DTYPE[self.dtype])  # F4E2M1: the packed bytes
         _lib.call("fmi_dev_d2h_async", out.ctypes.data, self.ptr, self.nbytes, _sptr(stream))
         _lib.call("fmi_stream_sync", _sptr(stream))
         return out
 
     def fill_synthetic(self, seed: int, peer: int, stream=None, first: int = 0) -> "Bucket":
         """Elements [first, first + n) of peer `peer`'s synthetic bucket (SURVEY.md §8d generator)."""
+        refuse_fp4("fill_synthetic", self)
         _lib.call("fmi_dev_fill_synthetic_at", int(self.dtype), self.ptr, self.n, seed, peer, int(first),
                   _sptr(stream))
         return self
@@ -344,6 +392,7 @@ class Event:
 def reduce_pair(op: Op, inout: Bucket, src: Bucket, n: Optional[int] = None, stream=None) -> None:
     """inout = op(inout, src) elementwise — one reference `f.f(a, b)` (include/Communicator.h:180-189)."""
     n = inout.n if n is None else n
+    refuse_fp4("reduce_pair", inout, src)
     if src.dtype != inout.dtype or src.n < n or inout.n < n:
         raise ValueError("reduce_pair: buckets must share dtype and hold n elements")
     _lib.call("fmi_dev_reduce_pair", int(op), int(inout.dtype), inout.ptr, src.ptr, n, _sptr(stream))
@@ -360,6 +409,7 @@ def reduce_pair_batch(op: Op, pairs: Sequence, stream=None) -> None:
         return
     dtype = pairs[0][0].dtype
     for a, b in pairs:
+        refuse_fp4("reduce_pair_batch", a, b)
         if a.dtype != dtype or b.dtype != dtype or b.n < a.n:
             raise ValueError("reduce_pair_batch: one dtype for every bucket, and each `in` at least as long as its inout")
     descs = (_PairDesc * len(pairs))(*[_PairDesc(a.ptr, b.ptr, a.n) for a, b in pairs])
@@ -368,6 +418,7 @@ def reduce_pair_batch(op: Op, pairs: Sequence, stream=None) -> None:
 
 
 def combine(op: Op, out: Bucket, a: Bucket, b: Bucket, stream=None) -> None:
+    refuse_fp4("combine", out, a, b)
     if not (out.dtype == a.dtype == b.dtype) or not (out.n == a.n == b.n):
         raise ValueError("combine: buckets must share dtype and length")
     _lib.call("fmi_dev_combine", int(op), int(out.dtype), out.ptr, a.ptr, b.ptr, out.n, _sptr(stream))
@@ -384,6 +435,7 @@ def reduce_tree(op: Op, alg: Alg, out: Bucket, ins: Sequence[Bucket], rank: int 
                 accumulate_f32: bool = False) -> None:
     """P-way reduction with a reference collective's bracketing (see include/fmi_dev.h). accumulate_f32 (F16 / BF16 /
     F8E4M3 / F8E5M2 buckets): the same program on f32 values, the result rounded to the storage type once."""
+    refuse_fp4("reduce_tree", out, *ins)
     dtype = acc_dtype(out.dtype, accumulate_f32)
     _check_peers(out, ins)
     _lib.call("fmi_dev_reduce_tree", int(op), dtype, int(alg), out.ptr, _ptr_array(ins), len(ins), rank,
@@ -435,14 +487,16 @@ def _mx_scales(b, what: str, n: int) -> int:
 
 
 def _mx_elements(who: str, what: str, b: Bucket) -> DType:
-    if b.dtype not in (DType.F8E4M3, DType.F8E5M2):
-        raise ValueError(f"{who} needs F8E4M3 or F8E5M2 {what}, got {DType(b.dtype).name}")
+    if b.dtype not in (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1):
+        raise ValueError(f"{who} needs F8E4M3 or F8E5M2 {what}, got {DType(b.dtype).name}; F4E2M1 (MXFP4) is the third "
+                         f"element type an MX bucket can have")
     return b.dtype
 
 
 def reduce_tree_mx(op: Op, alg: Alg, out: Bucket, out_scales: Optional[Bucket], ins: Sequence[Bucket],
                    in_scales: Sequence[Bucket], rank: int = 0, stream=None) -> None:
-    """The sum (Op.SUM) or mean (Op.AVG) of block-scaled (MX) F8E4M3 / F8E5M2 buckets (fmi_dev_reduce_tree_mx): every
+    """The sum (Op.SUM) or mean (Op.AVG) of block-scaled (MX) F8E4M3 / F8E5M2 (MXFP8) or F4E2M1 (MXFP4, packed two
+    elements to a byte; the scale rule at EMAX = 2) buckets (fmi_dev_reduce_tree_mx): every
     input element times its block's E8M0 scale in f32, the f32 SUM program of `alg`, then either stored as F32 (`out` an
     F32 bucket, out_scales None) or requantized: per block of 32 the smallest power-of-two scale that brings the block's
     largest magnitude within the element type, into `out_scales`, and the scaled sum narrowed into `out`. in_scales[p]
@@ -487,6 +541,7 @@ def mean_scale(inout: Bucket, P: int, n: Optional[int] = None, stream=None) -> N
     """inout = inout * fl(1 / P) in place (fmi_dev_mean_scale): Op.AVG's last step alone, for a SUM that went through
     an exchange of the caller's own. Float buckets; f16 / bf16 multiply in f32 and round to storage once."""
     n = inout.n if n is None else n
+    refuse_fp4("mean_scale", inout)
     if inout.n < n:
         raise ValueError("mean_scale: the bucket must hold n elements")
     _lib.call("fmi_dev_mean_scale", int(inout.dtype), inout.ptr, n, int(P), _sptr(stream))
@@ -497,6 +552,7 @@ def convert(dst: Bucket, src: Bucket, n: Optional[int] = None, stream=None) -> N
     through f32, one rounding in all (to the 8-bit floats non-saturating). How f32 / bf16 data gets into an 8-bit float
     bucket. dst may be src at equal element size."""
     n = dst.n if n is None else n
+    refuse_fp4("convert", dst, src)
     if dst.n < n or src.n < n:
         raise ValueError("convert: both buckets must hold n elements")
     _lib.call("fmi_dev_convert", int(dst.dtype), dst.ptr, int(src.dtype), src.ptr, n, _sptr(stream))
@@ -508,6 +564,7 @@ def scan_peers(op: Op, alg: Alg, outs: Sequence[Bucket], ins: Sequence[Bucket], 
     BF16 / F8E4M3 / F8E5M2 buckets): the same program on f32 values, every prefix rounded to the storage type once."""
     if len(outs) != len(ins):
         raise ValueError("scan_peers: one output bucket per peer")
+    refuse_fp4("scan_peers", *outs, *ins)
     dtype = acc_dtype(outs[0].dtype, accumulate_f32)
     _check_peers(outs[0], ins)  # O(P): every bucket, in or out, against the first output
     _check_peers(outs[0], outs)
@@ -524,6 +581,8 @@ def host_reduce_pair(op: Op, inout: np.ndarray, src: np.ndarray, dtype: Optional
     if not (inout.flags.c_contiguous and src.flags.c_contiguous):
         raise ValueError("host_reduce_pair: arrays must be contiguous")
     dt = dtype_of(inout) if dtype is None else DType(dtype)
+    if dt == DType.F4E2M1:
+        raise ValueError("host_reduce_pair: F4E2M1 is valid only in the MX calls")
     if np.dtype(_HOST_DTYPE[dt]).itemsize != inout.dtype.itemsize:
         raise ValueError("host_reduce_pair: the arrays' element size is not the dtype's")
     _lib.call("fmi_host_reduce_pair", int(op), int(dt), inout.ctypes.data, src.ctypes.data, inout.size)

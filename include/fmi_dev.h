@@ -133,11 +133,24 @@ typedef enum { FMI_OP_SUM = 0, FMI_OP_PROD = 1, FMI_OP_MAX = 2, FMI_OP_MIN = 3, 
  * take), and round the running value to 4 (E4M3) or 3 (E5M2) significant bits per combine; the form exists because it
  * is what the reference's template computes at such an element type. FMI_OP_AVG is valid on both, plain and with the
  * flag, by its definition: V = f32, store = narrow. fmi_dev_convert (below) moves f32 / f16 / bf16 data into and out
- * of such buckets. Additive: fmi_abi_version() stays 1. */
+ * of such buckets. Additive: fmi_abi_version() stays 1.
+ *
+ * FMI_F4E2M1 = 15: the OCP 4-bit float E2M1, the element of an MXFP4 bucket. 1 sign bit, 2 exponent bits (bias 1),
+ * 1 mantissa bit: the magnitudes of codes 0..7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6; bit 3 is the sign (so -0 exists); no
+ * inf, no NaN. Two elements to a byte: a bucket of n elements is ceil(n / 2) bytes, element 2k in bits 3:0 of byte k,
+ * element 2k + 1 in bits 7:4; for odd n the last byte's high nibble is ignored on input and written as 0 on output.
+ * Widen is the 16-entry table (exact). Narrow (f32 -> E2M1) is round-to-nearest on the eight magnitudes with ties to
+ * the even CODE (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), the sign kept (-0.2 -> 0x8);
+ * it is defined for finite |y| <= 6 only, which is all the MX calls feed it.
+ * The type is valid ONLY as the `dtype` of the four MX calls (fmi_dev_reduce_tree_mx, fmi_dev_mx_quantize,
+ * fmi_dev_mx_dequantize, fmi_comm_allreduce_mx; there FMI_ACC_F32 on it is accepted and dropped). Every other entry
+ * point that takes a dtype answers FMI_ERR_INVALID with a message naming FMI_F4E2M1, on the host. Additive:
+ * fmi_abi_version() stays 1, no new symbol. */
 typedef enum {
     FMI_F32 = 0, FMI_F64 = 1, FMI_I32 = 2, FMI_I64 = 3,
     FMI_U32 = 4, FMI_U64 = 5, FMI_I8 = 6, FMI_U8 = 7, FMI_I16 = 8, FMI_U16 = 9,
-    FMI_F16 = 10, FMI_BF16 = 11, FMI_F8E4M3 = 12, FMI_F8E5M2 = 13
+    FMI_F16 = 10, FMI_BF16 = 11, FMI_F8E4M3 = 12, FMI_F8E5M2 = 13,
+    FMI_F4E2M1 = 15
 } fmi_dtype_t;
 /* Reserved, NOT an fmi_dtype_t: FMI_F8E8M0 = 14 is the label the Python binding gives the scale bytes of an MX bucket
  * (DType.F8E8M0, bytes over np.uint8; fmi_dev_reduce_tree_mx below). No C-ABI call takes it as a dtype: every one
@@ -169,7 +182,7 @@ typedef enum {
  * _scan) accept it: the wire keeps the storage type (16-bit or 8-bit) and only the shard step changes; every rank passes the same dtype argument,
  * as every other argument. FMI_PATH_RCCL with the flag (SUM / PROD) is FMI_ERR_UNSUPPORTED: RCCL's reduction has its
  * own order and rounding. Additive: fmi_abi_version() stays 1, no new symbol. */
-#define FMI_ACC_F32 0x100   /* valid only on FMI_F16, FMI_BF16, FMI_F8E4M3 and FMI_F8E5M2 */
+#define FMI_ACC_F32 0x100   /* valid only on FMI_F16, FMI_BF16, FMI_F8E4M3 and FMI_F8E5M2 (and dropped by the MX calls) */
 
 /* Evaluation orders reproduced by the P-way kernels; each is the combine order of one reference
  * collective, so a P-bucket reduction on one device is bit-identical to the distributed one. */
@@ -392,20 +405,35 @@ int fmi_dev_reduce_tree_scaled(int op, int dtype, int alg, int out_dtype, void* 
  * and the inverse scale is a normal f32. Every operation is round-to-nearest-even with subnormals kept and no
  * contraction; the result does not depend on any order beyond the program's bracketing (deterministic, no atomics).
  * Valid: op FMI_OP_SUM or FMI_OP_AVG (PROD / MAX / MIN: FMI_ERR_INVALID); alg FMI_ALG_ALLREDUCE, _REDUCE or _REDUCE_LTR
- * with `rank` as in fmi_dev_reduce_tree (the scans: FMI_ERR_INVALID); dtype one of the two 8-bit floats (FMI_ACC_F32 is
- * accepted and dropped); out_dtype == dtype or FMI_F32; out_scales may be NULL only with FMI_F32; P >= 1, and P = 1 is
+ * with `rank` as in fmi_dev_reduce_tree (the scans: FMI_ERR_INVALID); dtype one of the two 8-bit floats, or FMI_F4E2M1
+ * (MXFP4, below) (FMI_ACC_F32 is accepted and dropped); out_dtype == dtype or FMI_F32; out_scales may be NULL only with FMI_F32; P >= 1, and P = 1 is
  * NOT a copy: it requantizes. All of it is checked on the host before a device is needed. ins[p] / in_scales[p]: peer
  * p's elements and scale bytes. out may alias an ins[p], and out_scales an in_scales[p], where out_dtype == dtype.
  * 2 <= P <= 16 with the element buckets 16-B aligned (scale arrays: any alignment): ONE fused kernel, graph-capturable,
  * no atomics, no temporaries. Any other call (P = 1, P > 16, unaligned buckets) dequantizes every input into an f32
  * temporary (FMI_ACC_F32's allocation: not capturable), runs the library's own FMI_F32 program and quantizes: the same
- * bits by construction. Additive: fmi_abi_version() stays 1. */
+ * bits by construction. Additive: fmi_abi_version() stays 1.
+ *
+ * MXFP4: dtype FMI_F4E2M1 (the encoding and packing at fmi_dtype_t). An MXFP4 bucket of n elements is ceil(n / 2)
+ * element bytes and ceil(n / 32) scale bytes; n counts ELEMENTS in every MX call. The text above holds with three
+ * type-specific pieces:
+ *   - widen is the 16-entry table; v_p = fl32(widen(x) * scale32(e)) is exact except 2 * 2^127 and above, which give
+ *     +-inf; e = 255 gives NaN for every nibble, zeros included; e = 0 is 2^-127, so 0.5 * 2^-127 is the subnormal 2^-128;
+ *   - EMAX = 2: the largest finite element is 6 = 1.5 * 2^2 (mantissa bits 0x400000), so
+ *         e_out = 255 if f == 255, otherwise max( f - 2 + (m > 0x400000), 0 )
+ *     e_out <= 253 for a finite block, the inverse scale is a normal f32 and |S * inv| <= 6 for every element;
+ *   - a block with e_out == 255 stores the scale byte 255 and every element nibble as 0 (E2M1 has no NaN; by the MX
+ *     rule a NaN scale makes the block NaN, and dequantizing it gives NaN by the multiply above).
+ * out_dtype == FMI_F4E2M1 or FMI_F32; the fused kernel needs the element buckets 16-B aligned (a block of 32 elements is
+ * one 16-B word); the fallback and the two conversions take any BYTE alignment. out may alias an input where the types
+ * agree. No byte beyond ceil(n / 2) and no scale byte beyond ceil(n / 32) is touched. */
 int fmi_dev_reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* out_scales, const void* const* ins,
                            const void* const* in_scales, int P, int rank, size_t n, fmi_stream_t stream);
 /* The fallback's two kernels made public, as fmi_dev_convert is. The non-MX side (src_dtype / dst_dtype) is FMI_F32,
  * FMI_F16 or FMI_BF16. Quantize: the out_dtype == dtype branch above applied to S = widen(src[i]) (exact). Dequantize:
  * dst[i] = narrow_dst( fl32( widen(src[i]) * scale32(src_scales[i / 32]) ) ). Any alignment, n = 0 succeeds, one launch
- * each, graph-capturable. */
+ * each, graph-capturable. dtype FMI_F4E2M1: the packed MXFP4 side, n counting elements ((n + 1) / 2 bytes; an odd
+ * bucket's last high nibble is written 0 by quantize and ignored by dequantize), any byte alignment. */
 int fmi_dev_mx_quantize(int dtype, void* out, void* out_scales, int src_dtype, const void* src, size_t n, fmi_stream_t stream);
 int fmi_dev_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const void* src_scales, size_t n, fmi_stream_t stream);
 
@@ -529,7 +557,8 @@ int fmi_comm_allreduce_scaled(fmi_comm_t comm, int op, int dtype, int alg, int o
  * between owners. Each owner runs fmi_dev_reduce_tree_mx at P = N, rank 0, on its shard's TRUE length (padding never
  * enters a block's amax); element and scale shards are then all-gathered. Every rank's recv / recv_scales is the
  * definition over the ranks' buckets in rank order. send / send_scales are not modified. A one-rank communicator runs
- * the P = 1 form. */
+ * the P = 1 form. FMI_F4E2M1: the same route at half the element bytes (a shard of 64 k elements is 32 k bytes); only the
+ * last non-empty shard can have an odd true length. */
 int fmi_comm_allreduce_mx(fmi_comm_t comm, int op, int dtype, int alg, int out_dtype, const void* send,
                           const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream);
 /* Host-ingress allreduce (BASELINE config C5): `send` / `recv` are HOST buckets, i.e. the channel recv

@@ -7,13 +7,15 @@ remarks as tools/half_resource_usage.py does it (each unit compiled device-only 
     python3 tools/fp8_resource_usage.py                  # every fp8_acc_kernel at P = 8 and P = 16, and the conversions
     python3 tools/fp8_resource_usage.py --all            # every P
     python3 tools/fp8_resource_usage.py --mx             # the fused MX units (fmi_fused_mx_*.hip) and fmi_mx.hip instead:
-                                                         # fp8_mx_kernel at P = 8 and 16, the quantize / dequantize kernels
+                                                         # fp8_mx_kernel / mxfp4_kernel at P = 8 and 16, the quantize / dequantize kernels
     python3 tools/fp8_resource_usage.py --isa            # instruction counts of the 8-way allreduce SUM kernels' loop
                                                          # (e4m3, e5m2 and the bf16 acc32 kernel beside them)
 
 Lines: fp8_acc_kernel<op, dtype, alg, P, scan>: vgpr .. agpr .. scratch .. occupancy ..
 (alg: 0 allreduce, 1 reduce, 2 reduce_ltr, 3 scan, 4 scan_ltr, 8 reduce partials);
-fp8_mx_kernel<dtype, alg, P, out32>, mx_quantize_kernel<dtype, source>, mx_dequantize_kernel<dtype, destination>.
+fp8_mx_kernel<dtype, alg, P, out32>, mx_quantize_kernel<dtype, source>, mx_dequantize_kernel<dtype, destination>;
+mxfp4_kernel<alg, P, out32>, mxfp4_quantize_kernel<source>, mxfp4_dequantize_kernel<destination> (the MXFP4 units,
+fmi_fused_mxfp4_*.hip, are part of --mx).
 """
 import argparse
 import concurrent.futures
@@ -45,6 +47,12 @@ def describe(mangled):
     m = re.search(r"\d+(mx_quantize_kernel|mx_dequantize_kernel)INS\d*_(6f8e4m3|6f8e5m2)E(DF16_|DF16b|f)EE", mangled)
     if m:
         return m.group(1), 0, f"{FP8[m.group(2)]}, {OTHER[m.group(3)]}"
+    m = re.search(r"12mxfp4_kernelILi(\d+)ELi(\d+)ELb([01])EEE", mangled)
+    if m:
+        return "mxfp4_kernel", int(m.group(2)), f"{m.group(1)}, {m.group(2)}, {'true' if m.group(3) == '1' else 'false'}"
+    m = re.search(r"\d+(mxfp4_quantize_kernel|mxfp4_dequantize_kernel)I(DF16_|DF16b|f)EE", mangled)
+    if m:
+        return m.group(1), 0, OTHER[m.group(2)]
     return None
 
 
@@ -88,7 +96,8 @@ def main():
     if a.isa:
         return isa()
     if a.mx:
-        srcs = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "fmi_fused_mx_*.hip"))) + ["fmi_mx.hip"]
+        srcs = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "fmi_fused_mx_*.hip")) +
+                      glob.glob(os.path.join(CSRC, "fmi_fused_mxfp4_*.hip"))) + ["fmi_mx.hip"]
     else:
         srcs = sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "fmi_fused_fp8_acc32_*.hip"))) + ["fmi_acc32_convert.hip"]
     with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
@@ -96,10 +105,10 @@ def main():
     shown = spilled = 0
     for k in kernels:
         d = describe(k["name"])
-        if d is None or (d[0].endswith("mx_kernel") or d[0].startswith("mx_")) != a.mx:
+        if d is None or (d[0].endswith("mx_kernel") or d[0].startswith("mx")) != a.mx:
             continue
         spilled += k["scratch"] != 0
-        if d[0] in ("fp8_acc_kernel", "fp8_mx_kernel") and not a.all and d[1] not in (8, 16):
+        if d[0] in ("fp8_acc_kernel", "fp8_mx_kernel", "mxfp4_kernel") and not a.all and d[1] not in (8, 16):
             continue
         shown += 1
         print(f"{d[0]}<{d[2]}>: vgpr {k['vgpr']} agpr {k['agpr']} scratch {k['scratch']} occupancy {k['occ']}")

@@ -15,6 +15,19 @@ n + n / 32 or 4 n out), the ratio of the ELEMENT rate to the yardstick's of the 
 spread over the passes.
 
     python3 tools/mx_bench.py [--kind e4m3] [--label NAME] [--out profiles/mx_bench.jsonl]
+
+--kind e2m1: the fused MXFP4 kernel (FMI_F4E2M1 elements, two to a byte) instead, with the unchanged fused MXFP8 E4M3
+kernel as the yardstick, in the same passes and at the same ELEMENT count (so the MXFP4 buckets are half the bytes):
+
+  mx                reduce_tree_mx on E4M3 buckets, out = E4M3 with scale bytes (the yardstick)
+  mxfp4             reduce_tree_mx on F4E2M1 buckets, out = F4E2M1 with scale bytes: the fused kernel
+  mx_f32            the yardstick's kernel with an F32 output: what mxfp4_f32 stands beside (both store 4 n bytes)
+  mxfp4_f32         the fused MXFP4 kernel with an F32 output
+  mxfp4_fallback    the same buckets one byte off 16-B alignment
+
+Bytes with the scale bytes counted: inputs P * (n / 2 + n / 32), output n / 2 + n / 32 or 4 n.
+
+    python3 tools/mx_bench.py --kind e2m1 [--label NAME] [--out profiles/mxfp4_bench.jsonl]
 """
 import argparse
 import os
@@ -34,9 +47,72 @@ ROWS = ("scaled", "mx", "mx_f32", "mx_fallback")  # the first is the yardstick
 PEAK = 8e12
 
 
+FP4_ROWS = ("mx", "mxfp4", "mx_f32", "mxfp4_f32", "mxfp4_fallback")  # the first is the yardstick
+
+
+def main_e2m1(args):
+    """n ELEMENTS per peer: E4M3 buckets of n bytes for the yardstick, F4E2M1 buckets of n / 2 bytes."""
+    P, n, S = args.peers, args.mib * MIB, args.sets
+    nb = fmi_amd.mx_blocks(n)
+    rows = [r for r in FP4_ROWS if r == FP4_ROWS[0] or r in args.rows.split(",")]
+    g8 = [Bucket.group(P + 1, n, DType.F8E4M3) for _ in range(S)]
+    # 16 spare bytes (32 elements) per bucket: the fallback's buckets are the same allocations one byte in
+    g4 = [Bucket.group(P + 1, n + 32, DType.F4E2M1) for _ in range(S)]
+    aligned = [[b.view(0, n) for b in g] for g in g4]
+    shifted = [[b.view(2, n) for b in g] for g in g4]
+    wide = [Bucket(n, np.float32) for _ in range(S)]
+    rng = np.random.default_rng(3)
+    packed = rng.integers(0, 256, n // 2 + 16, dtype=np.uint8)  # every nibble; the buckets differ by a rotation of the codes
+    scale_sets = []
+    for k in range(S):
+        for p in range(P):
+            g8[k][p].fill_synthetic(11, p)
+            g4[k][p].upload(packed ^ np.uint8(17 * (k * P + p) & 0xFF))
+        scale_sets.append([Bucket(nb, DType.F8E8M0) for _ in range(P + 1)])
+        for b in scale_sets[-1][:P]:
+            b.upload(rng.integers(120, 135, nb).astype(np.uint8))
+    fmi_amd.sync()
+    tree = lambda out, osc, ins, k: fmi_amd.reduce_tree_mx(Op.SUM, Alg.ALLREDUCE, out, osc, ins, scale_sets[k % S][:P])  # noqa: E731
+    launches = {
+        "mx": lambda k: tree(g8[k % S][P], scale_sets[k % S][P], g8[k % S][:P], k),
+        "mxfp4": lambda k: tree(aligned[k % S][P], scale_sets[k % S][P], aligned[k % S][:P], k),
+        "mx_f32": lambda k: tree(wide[k % S], None, g8[k % S][:P], k),
+        "mxfp4_f32": lambda k: tree(wide[k % S], None, aligned[k % S][:P], k),
+        "mxfp4_fallback": lambda k: tree(shifted[k % S][P], scale_sets[k % S][P], shifted[k % S][:P], k),
+    }
+    algo = {"mx": P * (n + nb) + n + nb, "mx_f32": P * (n + nb) + 4 * n, "mxfp4": P * (n // 2 + nb) + n // 2 + nb, "mxfp4_f32": P * (n // 2 + nb) + 4 * n,
+            "mxfp4_fallback": P * (n // 2 + nb) + n // 2 + nb}
+    iters = {r: args.fallback_iters if r == "mxfp4_fallback" else args.iters for r in FP4_ROWS}
+    ms = {r: [] for r in rows}
+    for _ in range(PASSES):
+        for r in rows:
+            ms[r].append(timed(launches[r], iters[r], S))
+    spread = lambda xs: round((max(xs) - min(xs)) / statistics.median(xs), 4)  # noqa: E731
+    elem = {r: [n / (m * 1e-3) for m in ms[r]] for r in rows}
+    lines = []
+    for r in rows:
+        byte_rate = [algo[r] / (m * 1e-3) for m in ms[r]]
+        ratios = [a / b for a, b in zip(elem[r], elem[FP4_ROWS[0]])]
+        lines.append({"tool": "tools/mx_bench.py --kind e2m1", "label": args.label, "inflight_kib": fmi_amd.tune_get(fmi_amd.Tune.FUSED_INFLIGHT_KIB),
+                      "kernel": f"tree{P} {'e4m3' if r in ('mx', 'mx_f32') else 'e2m1'} {r}", "elements_per_peer": n, "algorithmic_bytes": algo[r],
+                      "bytes_per_element": round(algo[r] / n, 4),
+                      "iters_per_pass": iters[r], "passes": PASSES, "rotating_sets": S, "ms_per_pass": [round(m, 4) for m in ms[r]],
+                      "Gelem_s_per_pass": [round(x / 1e9, 2) for x in elem[r]], "Gelem_s": round(statistics.median(elem[r]) / 1e9, 2),
+                      "GB_s_per_pass": [round(x / 1e9, 1) for x in byte_rate], "GB_s": round(statistics.median(byte_rate) / 1e9, 1),
+                      "fraction_of_8TBs": round(statistics.median(byte_rate) / PEAK, 4), "spread": spread(byte_rate),
+                      "yardstick": f"tree{P} e4m3 mx (the fused MXFP8 kernel), same passes, same element count, element rate",
+                      "element_rate_ratio_to_mxfp8_per_pass": [round(x, 4) for x in ratios],
+                      "element_rate_ratio_to_mxfp8": round(statistics.median(ratios), 4), "mxfp8_spread": spread(elem[FP4_ROWS[0]]),
+                      "timing": "two HIP events around back-to-back launches on the library stream"})
+    emit(lines, args.out)
+    for b in [b for g in g8 + g4 for b in g] + wide + [b for s in scale_sets for b in s]:
+        b.free()
+    fmi_amd.sync()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", default="e4m3", choices=("e4m3", "e5m2"))
+    ap.add_argument("--kind", default="e4m3", choices=("e4m3", "e5m2", "e2m1"))
     ap.add_argument("--mib", type=int, default=256, help="element bytes per input bucket")
     ap.add_argument("--peers", type=int, default=8)
     ap.add_argument("--sets", type=int, default=3)
@@ -47,6 +123,10 @@ def main():
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     fmi_amd.init(0)
+    if args.kind == "e2m1":
+        if args.rows == ",".join(ROWS):
+            args.rows = ",".join(FP4_ROWS)
+        return main_e2m1(args)
     dt = DType.F8E4M3 if args.kind == "e4m3" else DType.F8E5M2
     P, n, S = args.peers, args.mib * MIB, args.sets
     nb = fmi_amd.mx_blocks(n)
