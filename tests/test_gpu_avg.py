@@ -13,6 +13,7 @@ import fmi_amd
 from fmi_amd import Alg, Bucket, DType, Graph, Op, Stream, Tune
 from fmi_amd.comm import Comm, Path, Transport, unique_id
 from tests import _avg as G
+from tests import _guard
 from tests import _half as H
 from tests import _half_acc as A
 
@@ -62,19 +63,19 @@ def upload(src, kind, n, P, seed):
 
 def check_trees(src, kind, acc, n, P, seed, ranks=None, what=""):
     """ALLREDUCE at `ranks` (default: every rank), REDUCE at the same roots, REDUCE_LTR."""
-    ins, out = upload(src, kind, n, P, seed), Bucket(n, DT[kind])
+    ins = upload(src, kind, n, P, seed)
     kw = {"accumulate_f32": True} if acc else {}
     tag = f"{what}{src} {kind}{' acc32' if acc else ''} P={P} n={n}"
+
+    def check(alg, w, rank, name):
+        """One call into a guarded, poisoned output (tests/_guard.py), compared bit for bit."""
+        for got in _guard.launched(w, n, DT[kind], lambda out: fmi_amd.reduce_tree(Op.AVG, alg, out, ins, rank=rank, **kw), name):
+            G.assert_same(got.view(np.uint16) if G.is_half(kind) else got, w, kind, name)
+
     for r in (range(P) if ranks is None else ranks):
-        fmi_amd.reduce_tree(Op.AVG, Alg.ALLREDUCE, out, ins, rank=r, **kw)
-        fmi_amd.sync()
-        G.assert_same(read(out, kind), want("allreduce", src, kind, acc, n, P, seed)[r], kind, f"allreduce {tag} rank {r}")
-        fmi_amd.reduce_tree(Op.AVG, Alg.REDUCE, out, ins, rank=r, **kw)
-        fmi_amd.sync()
-        G.assert_same(read(out, kind), want("reduce", src, kind, acc, n, P, seed, r), kind, f"reduce {tag} root {r}")
-    fmi_amd.reduce_tree(Op.AVG, Alg.REDUCE_LTR, out, ins, **kw)
-    fmi_amd.sync()
-    G.assert_same(read(out, kind), want("reduce_ltr", src, kind, acc, n, P, seed), kind, f"reduce_ltr {tag}")
+        check(Alg.ALLREDUCE, want("allreduce", src, kind, acc, n, P, seed)[r], r, f"allreduce {tag} rank {r}")
+        check(Alg.REDUCE, want("reduce", src, kind, acc, n, P, seed, r), r, f"reduce {tag} root {r}")
+    check(Alg.REDUCE_LTR, want("reduce_ltr", src, kind, acc, n, P, seed), 0, f"reduce_ltr {tag}")
 
 
 @pytest.fixture(params=[0, 2], ids=["global_nt", "buffer_sc1"])

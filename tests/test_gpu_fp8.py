@@ -14,6 +14,7 @@ import fmi_amd
 from fmi_amd import Alg, Bucket, DType, Graph, Op, PinnedArray, Stream
 from fmi_amd.comm import Path
 from tests import _fp8 as F
+from tests import _guard as G
 from tests import _half as H
 
 pytestmark = pytest.mark.gpu
@@ -271,29 +272,30 @@ def upload(src, kind, n, P, seed, offset=0):
 
 
 def check_trees(want, src, kind, op, n, P, seed, acc, roots=None, ranks=None, offset=0, what=""):
-    ins, out = upload(src, kind, n, P, seed, offset), empty(n, kind, offset)
+    ins = upload(src, kind, n, P, seed, offset)
     tag = f"{what}{src} {kind} {op} P={P} n={n} acc={acc}"
+
+    def check(alg, w, rank, name):
+        """One call into a guarded, poisoned output `offset` bytes off alignment (tests/_guard.py), compared on its bytes."""
+        for got in G.launched(w, n, DT[kind], lambda out: fmi_amd.reduce_tree(OP[op], alg, out, ins, rank=rank, accumulate_f32=acc),
+                              name, offset):
+            F.assert_bits(got, w, kind, name)
+
     for r in (sorted({0, 1, P - 1}) if ranks is None else ranks):
-        fmi_amd.reduce_tree(OP[op], Alg.ALLREDUCE, out, ins, rank=r, accumulate_f32=acc)
-        fmi_amd.sync()
-        F.assert_bits(read(out), want("allreduce", src, kind, op, n, P, seed)[r], kind, f"allreduce {tag} rank {r}")
+        check(Alg.ALLREDUCE, want("allreduce", src, kind, op, n, P, seed)[r], r, f"allreduce {tag} rank {r}")
     for root in (sorted({0, P - 1}) if roots is None else roots):
-        fmi_amd.reduce_tree(OP[op], Alg.REDUCE, out, ins, rank=root, accumulate_f32=acc)
-        fmi_amd.sync()
-        F.assert_bits(read(out), want("reduce", src, kind, op, n, P, seed, root)[0], kind, f"reduce {tag} root {root}")
-    fmi_amd.reduce_tree(OP[op], Alg.REDUCE_LTR, out, ins, accumulate_f32=acc)
-    fmi_amd.sync()
-    F.assert_bits(read(out), want("reduce_ltr", src, kind, op, n, P, seed), kind, f"reduce_ltr {tag}")
+        check(Alg.REDUCE, want("reduce", src, kind, op, n, P, seed, root)[0], root, f"reduce {tag} root {root}")
+    check(Alg.REDUCE_LTR, want("reduce_ltr", src, kind, op, n, P, seed), 0, f"reduce_ltr {tag}")
 
 
 def check_scans(want, src, kind, op, n, P, seed, acc, offset=0, what=""):
     for alg, family in ((Alg.SCAN, "scan"), (Alg.SCAN_LTR, "scan_ltr")):
-        ins, outs = upload(src, kind, n, P, seed, offset), [empty(n, kind, offset) for _ in range(P)]
-        fmi_amd.scan_peers(OP[op], alg, outs, ins, accumulate_f32=acc)
-        fmi_amd.sync()
-        w = want(family, src, kind, op, n, P, seed)
-        for r in range(P):
-            F.assert_bits(read(outs[r]), w[r], kind, f"{what}{family} {src} {kind} {op} P={P} n={n} acc={acc} output {r}")
+        ins, w = upload(src, kind, n, P, seed, offset), want(family, src, kind, op, n, P, seed)
+        tag = f"{what}{family} {src} {kind} {op} P={P} n={n} acc={acc}"
+        # every output guarded and poisoned (tests/_guard.py)
+        for got in G.launched_all(w, n, DT[kind], lambda outs: fmi_amd.scan_peers(OP[op], alg, outs, ins, accumulate_f32=acc), tag, offset):
+            for r in range(P):
+                F.assert_bits(got[r], w[r], kind, f"{tag} output {r}")
 
 
 @pytest.mark.parametrize("P", FUSED_P)

@@ -12,6 +12,7 @@ import fmi_amd
 from fmi_amd import Alg, Bucket, DType, Graph, Stream, Tune
 from tests import _fp8 as F
 from tests import _fp8_scaled as FS
+from tests import _guard as G
 
 pytestmark = pytest.mark.gpu
 
@@ -67,23 +68,31 @@ def read_word(b):
     return int(b.numpy().view(np.uint32)[0])
 
 
-def run(alg, kind, xs, s, t, out, root=0, amax_bits=0, offset=0, stream=None):
-    """One call on fresh buckets: (output, amax bits or None). amax_bits None: amax = NULL."""
+def run(alg, kind, xs, s, t, out, root=0, amax_bits=0, offset=0, stream=None, want=None, what=""):
+    """One call on fresh buckets: (output, amax bits or None). amax_bits None: amax = NULL. The output and the one-float
+    amax slot sit inside guarded allocations (tests/_guard.py): no byte around them may change. With `want` the output is
+    poisoned under the poison rule, the call made once per poison, and no element may be left unwritten."""
     n = xs[0].size
     ins = [bucket(x, kind, offset) for x in xs]
-    o = out_bucket(n, kind, out, offset if out == "same" else 0)
-    am = None if amax_bits is None else word(amax_bits)
-    fmi_amd.reduce_tree_scaled(alg, o, ins, f32_bucket(s), None if t is None else f32_bucket(t), am, rank=root, stream=stream)
-    fmi_amd.sync()
-    return read_out(o, out), (None if am is None else read_word(am))
+    dtype, off = (DT[kind], offset) if out == "same" else (DType.F32, 0)
+    for o in (G.guarded_runs(want, n, dtype, off) if want is not None else [G.Guarded(n, dtype, off)]):
+        am = None if amax_bits is None else G.Guarded(1, DType.F32, 7).load([np.array([amax_bits], np.uint32)])
+        fmi_amd.reduce_tree_scaled(alg, o.b, ins, f32_bucket(s), None if t is None else f32_bucket(t), None if am is None else am.b,
+                                   rank=root, stream=stream)
+        fmi_amd.sync()
+        got = o.read(want, what)
+        got_amax = None if am is None else int(am.read(None, f"{what} amax").view(np.uint32)[0])
+        if want is not None:
+            FS.assert_out(got, want, kind, out, what)
+    return got, got_amax
 
 
 def check(name, kind, xs, s, t, out, amax_bits=0, offset=0, what=""):
     family, alg, root_of = ALGS[name]
     root = root_of(len(xs))
     want, want_amax, _ = FS.expected_scaled(family, kind, xs, s, t, out, root)
-    got, got_amax = run(alg, kind, xs, s, t, out, root, amax_bits, offset)
     tag = f"{what} {kind} {name} P={len(xs)} n={xs[0].size} out={out} t={t}"
+    got, got_amax = run(alg, kind, xs, s, t, out, root, amax_bits, offset, want=want, what=tag)
     FS.assert_out(got, want, kind, out, tag)
     if amax_bits is not None:
         FS.assert_amax(got_amax, FS.fold_amax(amax_bits, want_amax), tag)

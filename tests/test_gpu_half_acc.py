@@ -14,6 +14,7 @@ import fmi_amd
 from fmi_amd import Alg, Bucket, Graph, Op, Stream, Tune
 from fmi_amd.comm import Path
 from oracle import fmi_oracle as orc
+from tests import _guard as G
 from tests import _half as H
 from tests import _half_acc as A
 from tests.test_gpu_half import DT, OP, bucket, read
@@ -49,31 +50,37 @@ def roots(P):
     return sorted({0, 5 % P, P - 1})
 
 
+def tree_into_guarded(alg, kind, op, ins, w, what, rank=0):
+    """One accumulate_f32 reduce_tree call into a guarded, poisoned output (tests/_guard.py), compared on its raw bits."""
+    for got in G.launched(w, w.size, DT[kind], lambda out: fmi_amd.reduce_tree(OP[op], alg, out, ins, rank=rank, accumulate_f32=True), what):
+        H.assert_bits(got.view(np.uint16), w, kind, op, what)
+
+
 def check_trees(src, kind, op, n, P, seed, what=""):
-    ins, out = upload(src, kind, n, P, seed), Bucket(n, DT[kind])
+    ins = upload(src, kind, n, P, seed)
     tag = f"{what}{src} {kind} {op} P={P} n={n}"
     for r in sorted({0, 1, P - 1}):
-        fmi_amd.reduce_tree(OP[op], Alg.ALLREDUCE, out, ins, rank=r, accumulate_f32=True)
-        fmi_amd.sync()
-        H.assert_bits(read(out), want("allreduce", src, kind, op, n, P, seed)[r], kind, op, f"allreduce {tag} rank {r}")
+        tree_into_guarded(Alg.ALLREDUCE, kind, op, ins, want("allreduce", src, kind, op, n, P, seed)[r], f"allreduce {tag} rank {r}", r)
     for root in roots(P):
-        fmi_amd.reduce_tree(OP[op], Alg.REDUCE, out, ins, rank=root, accumulate_f32=True)
-        fmi_amd.sync()
-        H.assert_bits(read(out), want("reduce", src, kind, op, n, P, seed, root)[0], kind, op, f"reduce {tag} root {root}")
-    fmi_amd.reduce_tree(OP[op], Alg.REDUCE_LTR, out, ins, accumulate_f32=True)
-    fmi_amd.sync()
-    H.assert_bits(read(out), want("reduce_ltr", src, kind, op, n, P, seed), kind, op, f"reduce_ltr {tag}")
+        tree_into_guarded(Alg.REDUCE, kind, op, ins, want("reduce", src, kind, op, n, P, seed, root)[0], f"reduce {tag} root {root}", root)
+    tree_into_guarded(Alg.REDUCE_LTR, kind, op, ins, want("reduce_ltr", src, kind, op, n, P, seed), f"reduce_ltr {tag}")
 
 
 def check_scans(src, kind, op, n, P, seed, what="", alias=False):
+    """Outputs of their own are guarded and poisoned; aliased ones are the inputs themselves."""
     for alg, family in ((Alg.SCAN, "scan"), (Alg.SCAN_LTR, "scan_ltr")):
         ins = upload(src, kind, n, P, seed)
-        outs = ins if alias else [Bucket(n, DT[kind]) for _ in range(P)]
-        fmi_amd.scan_peers(OP[op], alg, outs, ins, accumulate_f32=True)
-        fmi_amd.sync()
         w = want(family, src, kind, op, n, P, seed)
-        for r in range(P):
-            H.assert_bits(read(outs[r]), w[r], kind, op, f"{what}{family} {src} {kind} {op} P={P} n={n} output {r}")
+        if alias:
+            fmi_amd.scan_peers(OP[op], alg, ins, ins, accumulate_f32=True)
+            fmi_amd.sync()
+            gots = [[read(b) for b in ins]]
+        else:
+            gots = G.launched_all(w, n, DT[kind], lambda outs: fmi_amd.scan_peers(OP[op], alg, outs, ins, accumulate_f32=True),
+                                  f"{what}{family} {src} {kind} {op} P={P} n={n}")
+        for got in gots:
+            for r in range(P):
+                H.assert_bits(got[r].view(np.uint16), w[r], kind, op, f"{what}{family} {src} {kind} {op} P={P} n={n} output {r}")
 
 
 @pytest.fixture(params=[0, 2], ids=["global_nt", "buffer_sc1"])

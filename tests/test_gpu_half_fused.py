@@ -15,6 +15,7 @@ import fmi_amd
 from fmi_amd import Alg, Bucket, Graph, Op, Stream, Tune
 from fmi_amd.comm import Path
 from oracle import fmi_oracle as orc
+from tests import _guard as G
 from tests import _half as H
 from tests._half_fused_cases import (ALLREDUCE_P, LTR_P, REDUCE_P, SCAN_P, allreduce_ranks, extra_ops_at, reduce_roots)
 from tests.test_gpu_half import DT, FUSED_SIZES, OP, bucket, read
@@ -66,22 +67,32 @@ def upload(kind, n, P, seed):
 
 
 def run_scan(alg, kind, op, n, P, seed, what, alias=False):
+    """Outputs of their own are guarded and poisoned (tests/_guard.py); aliased ones are the inputs themselves."""
     ins = upload(kind, n, P, seed)
-    outs = ins if alias else [Bucket(n, DT[kind]) for _ in range(P)]
-    fmi_amd.scan_peers(OP[op], alg, outs, ins)
-    fmi_amd.sync()
     want = expected("scan" if alg == Alg.SCAN else "scan_ltr", kind, op, n, P, seed)
-    for r in range(P):
-        H.assert_bits(read(outs[r]), want[r], kind, op, f"{what} {kind} {op} P={P} n={n} output {r}")
+    if alias:
+        fmi_amd.scan_peers(OP[op], alg, ins, ins)
+        fmi_amd.sync()
+        gots = [[read(b) for b in ins]]
+    else:
+        gots = G.launched_all(want, n, DT[kind], lambda outs: fmi_amd.scan_peers(OP[op], alg, outs, ins),
+                              f"{what} {kind} {op} P={P} n={n}")
+    for got in gots:
+        for r in range(P):
+            H.assert_bits(got[r].view(np.uint16), want[r], kind, op, f"{what} {kind} {op} P={P} n={n} output {r}")
+
+
+def run_tree(alg, kind, op, ins, want, what, rank=0):
+    """One reduce_tree call into a guarded, poisoned output, compared on its 16 raw bits."""
+    for got in G.launched(want, want.size, DT[kind], lambda out: fmi_amd.reduce_tree(OP[op], alg, out, ins, rank=rank), what):
+        H.assert_bits(got.view(np.uint16), want, kind, op, what)
 
 
 def run_allreduce(kind, op, n, P, seed, what):
     want = expected("allreduce", kind, op, n, P, seed)
-    ins, out = upload(kind, n, P, seed), Bucket(n, DT[kind])
+    ins = upload(kind, n, P, seed)
     for r in allreduce_ranks(op, P):
-        fmi_amd.reduce_tree(OP[op], Alg.ALLREDUCE, out, ins, rank=r)
-        fmi_amd.sync()
-        H.assert_bits(read(out), want[r], kind, op, f"{what} {kind} {op} P={P} n={n} rank {r}")
+        run_tree(Alg.ALLREDUCE, kind, op, ins, want[r], f"{what} {kind} {op} P={P} n={n} rank {r}", rank=r)
     if op == "max":  # ±0 ties: a kernel that hands every rank rank 0's bits fails above only if the ranks differ
         assert any(not np.array_equal(want[0], want[r]) for r in range(1, P)), "at least two ranks must differ on ±0"
 
@@ -110,11 +121,8 @@ def test_reduce_ltr_and_scan_ltr(device, kind, P):
     """Fused up to 31 peers, the one-pass chain up to 128, segments with a carry-in beyond."""
     for op in ops_at("ltr", P):
         for n in sizes(P):
-            ins, out = upload(kind, n, P, seed=21), Bucket(n, DT[kind])
-            fmi_amd.reduce_tree(OP[op], Alg.REDUCE_LTR, out, ins)
-            fmi_amd.sync()
-            H.assert_bits(read(out), expected("reduce_ltr", kind, op, n, P, 21), kind, op,
-                          f"reduce_ltr {kind} {op} P={P} n={n}")
+            run_tree(Alg.REDUCE_LTR, kind, op, upload(kind, n, P, seed=21), expected("reduce_ltr", kind, op, n, P, 21),
+                     f"reduce_ltr {kind} {op} P={P} n={n}")
             run_scan(Alg.SCAN_LTR, kind, op, n, P, 21, "scan_ltr")
 
 
@@ -129,12 +137,10 @@ def test_scan_outputs_alias_inputs(device, kind):
 def test_reduce_wide_roots(device, kind, P):
     for op in ops_at("reduce", P):
         for n in sizes(P):
-            ins, out = upload(kind, n, P, seed=23), Bucket(n, DT[kind])
+            ins = upload(kind, n, P, seed=23)
             for root in reduce_roots(P):
-                fmi_amd.reduce_tree(OP[op], Alg.REDUCE, out, ins, rank=root)
-                fmi_amd.sync()
-                H.assert_bits(read(out), expected("reduce", kind, op, n, P, 23, root)[0], kind, op,
-                              f"reduce {kind} {op} P={P} n={n} root {root}")
+                run_tree(Alg.REDUCE, kind, op, ins, expected("reduce", kind, op, n, P, 23, root)[0],
+                         f"reduce {kind} {op} P={P} n={n} root {root}", rank=root)
 
 
 @pytest.mark.parametrize("P", ALLREDUCE_P)
@@ -172,10 +178,8 @@ def test_buffer_and_global_policy(fused_policy, kind):
     """One P per family of the kernels that take FMI_TUNE_FUSED_POLICY."""
     for op in ("sum", "max"):
         for n in WIDE_SIZES:
-            ins, out = upload(kind, n, 5, seed=21), Bucket(n, DT[kind])
-            fmi_amd.reduce_tree(OP[op], Alg.REDUCE_LTR, out, ins)
-            fmi_amd.sync()
-            H.assert_bits(read(out), expected("reduce_ltr", kind, op, n, 5, 21), kind, op, f"reduce_ltr P=5 n={n}")
+            run_tree(Alg.REDUCE_LTR, kind, op, upload(kind, n, 5, seed=21), expected("reduce_ltr", kind, op, n, 5, 21),
+                     f"reduce_ltr P=5 n={n}")
             run_scan(Alg.SCAN_LTR, kind, op, n, 16, 21, "scan_ltr")
             run_allreduce(kind, op, n, 24, 24, "allreduce")
             run_scan(Alg.SCAN, kind, op, n, 31, 25, "scan")

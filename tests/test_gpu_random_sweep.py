@@ -2,16 +2,16 @@
 cap — so single fused kernels, one-pass blocked kernels, fused 16-peer block launches over two and three
 levels, ragged last blocks, and the 8/16-bit pairwise-pass programs over run-time-sized schedules), algorithm, op, dtype, bucket
 length and element offset (aligned and unaligned views), every result bit-exact against the oracle's
-simulation of the reference collective. Deterministic: the case list is a function of the seed."""
+simulation of the reference collective, into guarded and poisoned outputs (tests/_guard.py). Deterministic: the case
+list is a function of the seed."""
 import os
 
 import numpy as np
 import pytest
 
-import fmi_amd
 from fmi_amd import Alg, Bucket
 from oracle import fmi_oracle as orc
-from tests.test_gpu_parity import ALL_DTYPES, OPNAME, OPS, assert_bit_equal, inputs
+from tests.test_gpu_parity import ALL_DTYPES, OPNAME, OPS, inputs, scan_into_guarded, tree_into_guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -54,14 +54,9 @@ def test_random_p_way_cases(device, seed):
             if alg in (Alg.SCAN, Alg.SCAN_LTR):
                 ordered = alg == Alg.SCAN_LTR
                 want, _ = orc.scan(ys, fn, commutative=not ordered, associative=not ordered)
-                outs = [Bucket(n, dtype) for _ in range(P)]
-                fmi_amd.scan_peers(op, alg, outs, ins)
-                for p in range(P):
-                    assert_bit_equal(outs[p].numpy(), want[p], f"{what} peer {p}")
+                scan_into_guarded(op, alg, ins, want, what)
                 done += 1
                 continue
-            out = Bucket(n, dtype)
-            fmi_amd.reduce_tree(op, alg, out, ins, rank=rank)
             if alg == Alg.ALLREDUCE:
                 want, _ = orc.allreduce(ys, fn)
                 want = want[rank]
@@ -69,7 +64,7 @@ def test_random_p_way_cases(device, seed):
                 want, _ = orc.reduce(ys, fn, root=rank)
             else:
                 want, _ = orc.reduce(ys, fn, root=0, commutative=False, associative=False)
-            assert_bit_equal(out.numpy(), want, what)
+            tree_into_guarded(op, alg, ins, want, rank, what)
             done += 1
     print(f"seed {seed}: {done} cases bit-exact")
     assert done == CASES
