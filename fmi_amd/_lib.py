@@ -101,6 +101,9 @@ SIGNATURES = {
     "fmi_dev_reduce_tree_mx": (_i, [_i, _i, _i, _i, _vp, _vp, _c.POINTER(_vp), _c.POINTER(_vp), _i, _i, _sz, _vp]),
     "fmi_dev_mx_quantize": (_i, [_i, _vp, _vp, _i, _vp, _sz, _vp]),
     "fmi_dev_mx_dequantize": (_i, [_i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "fmi_dev_reduce_tree_mx_sr": (_i, [_i, _i, _i, _vp, _vp, _c.POINTER(_vp), _c.POINTER(_vp), _vp, _c.c_uint64, _i, _i, _sz, _vp]),
+    "fmi_dev_mx_quantize_sr": (_i, [_i, _vp, _vp, _i, _vp, _sz, _vp, _c.c_uint64, _vp]),
+    "fmi_host_mx_quantize_sr": (_i, [_i, _vp, _vp, _c.POINTER(_c.c_float), _sz, _c.c_uint64, _c.c_uint64]),
     "fmi_host_reduce_pair": (_i, [_i, _i, _vp, _vp, _sz]),
     "fmi_host_device_ptr": (_i, [_vp, _sz, _c.POINTER(_vp)]),
     "fmi_host_page_locked": (_i, [_vp, _sz]),
@@ -119,6 +122,7 @@ SIGNATURES = {
     "fmi_comm_allreduce": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "fmi_comm_allreduce_scaled": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fmi_comm_allreduce_mx": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "fmi_comm_allreduce_mx_sr": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _c.c_uint64, _vp]),
     "fmi_comm_allreduce_host": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _sz]),
     "fmi_comm_reduce": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _i, _vp]),
     "fmi_comm_reduce_sendbuf": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _i, _vp]),

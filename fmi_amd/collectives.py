@@ -106,12 +106,15 @@ class HipEngine:
                   amax.data_ptr() if amax is not None else None, len(ins), rank, out.numel(), self._stream())
 
     def reduce_tree_mx(self, op: Op, alg: Alg, out: torch.Tensor, out_scales: Optional[torch.Tensor],
-                       ins: Sequence[torch.Tensor], in_scales: Sequence[torch.Tensor], rank: int = 0) -> None:
+                       ins: Sequence[torch.Tensor], in_scales: Sequence[torch.Tensor], rank: int = 0,
+                       seed: Optional[torch.Tensor] = None, first: int = 0) -> None:
         """The sum or mean of block-scaled (MX) float8 tensors (fmi_dev_reduce_tree_mx): `ins` are float8_e4m3fn /
         float8_e5m2 tensors, `in_scales` their float8_e8m0fnu (or uint8) scale tensors of ceil(n / 32) elements; `out` is
         a tensor of the inputs' dtype with `out_scales`, or of float32 with out_scales None. MXFP4: `ins` are
         float4_e2m1fn_x2 tensors (two elements per tensor element, so n = 2 * numel and a float32 `out` holds 2 * numel
-        values)."""
+        values). seed: a one-element int64 / uint64 device tensor selects stochastic rounding
+        (fmi_dev_reduce_tree_mx_sr; `out` of the inputs' dtype): its 64 bits, as they are, are the Philox key, read by the
+        kernel; `first`, a multiple of 32, is the stream position of element 0."""
         import ctypes
         dtype = _dtype(ins[0])
         if dtype not in (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1):
@@ -137,6 +140,15 @@ class HipEngine:
                 raise ValueError(f"reduce_tree_mx: {name} must hold ceil(n / 32) = {blocks} scale bytes, got {t.numel()}")
         ptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
         sptrs = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in in_scales])
+        if seed is not None:
+            seed_types = tuple(getattr(torch, k) for k in ("int64", "uint64") if hasattr(torch, k))
+            if seed.dtype not in seed_types or seed.numel() != 1 or not seed.is_cuda:
+                raise ValueError("reduce_tree_mx: seed must be a one-element int64 or uint64 device tensor")
+            if out.dtype == torch.float32:
+                raise ValueError("reduce_tree_mx: stochastic rounding needs an output of the inputs' dtype")
+            _lib.call("fmi_dev_reduce_tree_mx_sr", int(op), int(dtype), int(alg), out.data_ptr(), out_scales.data_ptr(), ptrs,
+                      sptrs, seed.data_ptr(), int(first), len(ins), rank, n, self._stream())
+            return
         _lib.call("fmi_dev_reduce_tree_mx", int(op), int(dtype), int(alg), int(_dtype(out)), out.data_ptr(),
                   out_scales.data_ptr() if out_scales is not None else None, ptrs, sptrs, len(ins), rank, n,
                   self._stream())

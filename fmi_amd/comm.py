@@ -18,7 +18,7 @@ import numpy as np
 
 from ._lib import Timeout  # noqa: F401 - FMI_ERR_TIMEOUT, the reference's FMI::Utils::Timeout
 
-from .device import (Alg, Bucket, DType, Op, _f32_word, _mx_elements, _mx_scales, _sptr, acc_dtype, dtype_of, itemsize_of,
+from .device import (Alg, Bucket, DType, Op, _f32_word, _mx_elements, _mx_scales, _sptr, _sr_seed, acc_dtype, dtype_of, itemsize_of,
                      refuse_fp4)
 
 ID_BYTES = 128
@@ -146,18 +146,27 @@ class Comm:
                   _f32_word(amax, "amax"), send.n, _sptr(stream))
 
     def allreduce_mx(self, op: Op, send: Bucket, send_scales: Bucket, recv: Bucket, recv_scales: Optional[Bucket] = None,
-                     ordered: bool = False, stream=None) -> None:
+                     ordered: bool = False, stream=None, seed: Optional[Bucket] = None, first: int = 0) -> None:
         """The sharded allreduce of MX buckets (fmi_comm_allreduce_mx, path TREE): the sum (Op.SUM) or mean (Op.AVG)
         over the ranks of `send` under its block scales `send_scales` (F8E8M0, ceil(n / 32) bytes), in the reference's
         order, into `recv` on every rank: an F32 bucket (recv_scales None), or a bucket of send's dtype requantized
         block by block with its scale bytes in `recv_scales`. The wire carries the element bytes and the scale bytes.
-        F4E2M1 buckets (MXFP4) travel packed, at half the element bytes."""
+        F4E2M1 buckets (MXFP4) travel packed, at half the element bytes.
+        seed: a U64 bucket of one element selects stochastic rounding (fmi_comm_allreduce_mx_sr; `recv` of send's dtype):
+        every rank holds the same value in it and passes the same `first`, a multiple of 32, and every rank's result is
+        device.reduce_tree_mx's over the ranks' buckets at that (seed, first)."""
         dtype = _mx_elements("allreduce_mx", "send bucket", send)
         if recv.n != send.n or recv.dtype not in (dtype, DType.F32):
             raise ValueError("allreduce_mx: `recv` must hold send's length in its dtype or in F32")
         if recv.dtype != DType.F32 and recv_scales is None:
             raise ValueError("allreduce_mx: recv_scales is missing: only an F32 output has no scale bytes")
         alg = Alg.REDUCE_LTR if ordered else Alg.ALLREDUCE
+        if seed is not None:
+            word = _sr_seed("allreduce_mx", seed, recv, first)
+            _lib.call("fmi_comm_allreduce_mx_sr", self.handle, int(op), int(dtype), int(alg), _p(send),
+                      _mx_scales(send_scales, "send_scales", send.n), _p(recv), _mx_scales(recv_scales, "recv_scales", send.n),
+                      send.n, word, int(first), _sptr(stream))
+            return
         _lib.call("fmi_comm_allreduce_mx", self.handle, int(op), int(dtype), int(alg), int(recv.dtype), _p(send),
                   _mx_scales(send_scales, "send_scales", send.n), _p(recv),
                   None if recv_scales is None else _mx_scales(recv_scales, "recv_scales", send.n), send.n, _sptr(stream))

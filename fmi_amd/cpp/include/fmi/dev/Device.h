@@ -427,11 +427,24 @@ inline std::size_t mx_blocks(std::size_t n) { return (n + 31) / 32; }
 // program of `alg` (`rank` as in fmi_dev_reduce_tree), then per block of 32 the smallest power-of-two scale that brings
 // the block's largest magnitude within the element type, into out_scales, and the scaled sum narrowed into `out`; or,
 // into a Bucket<float>, the sum itself and no output scales.
+// Stochastic rounding for the MX calls (fmi_dev_reduce_tree_mx_sr, fmi_dev_mx_quantize_sr): `seed` is ONE u64 in device
+// memory, read by the kernel (a captured graph replays with whatever it then holds); `first`, a multiple of 32, is the
+// stream position of the call's element 0. Passed last to Dev::reduce_tree_mx and Dev::mx_quantize, after the stream.
+struct Sr {
+    const Bucket<std::uint64_t>& seed;
+    std::uint64_t first = 0;
+};
+
 namespace detail {
+inline const std::uint64_t* sr_seed(const Sr& sr) {
+    if (sr.seed.size() != 1) throw std::runtime_error("Dev::Sr: the seed is a bucket of one std::uint64_t");
+    return sr.seed.data();
+}
+
 template <class A>
 inline void reduce_tree_mx(int op, int alg, int out_dtype, void* out, void* out_scales, std::size_t n,
                            const std::vector<const Bucket<A>*>& ins, const std::vector<const Bucket<float8_e8m0>*>& in_scales,
-                           int rank, fmi_stream_t stream) {
+                           int rank, fmi_stream_t stream, const Sr* sr = nullptr) {
     static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>,
                   "reduce_tree_mx: Dev::float8_e4m3 or Dev::float8_e5m2 elements");
     if (ins.empty() || ins.size() > static_cast<std::size_t>(std::numeric_limits<int>::max()) || in_scales.size() != ins.size())
@@ -443,6 +456,12 @@ inline void reduce_tree_mx(int op, int alg, int out_dtype, void* out, void* out_
             throw std::runtime_error("Dev::reduce_tree_mx: a scale bucket holds (n + 31) / 32 bytes");
         ptrs.push_back(ins[p]->data());
         sptrs.push_back(in_scales[p]->data());
+    }
+    if (sr) {
+        check(fmi_dev_reduce_tree_mx_sr(op, dtype_of<A>(), alg, out, out_scales, ptrs.data(), sptrs.data(), sr_seed(*sr), sr->first,
+                                        static_cast<int>(ins.size()), rank, n, stream),
+              "fmi_dev_reduce_tree_mx_sr");
+        return;
     }
     check(fmi_dev_reduce_tree_mx(op, dtype_of<A>(), alg, out_dtype, out, out_scales, ptrs.data(), sptrs.data(),
                                  static_cast<int>(ins.size()), rank, n, stream),
@@ -461,6 +480,13 @@ inline void reduce_tree_mx(int op, int alg, Bucket<float>& out, const std::vecto
                            const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank = 0, fmi_stream_t stream = nullptr) {
     detail::reduce_tree_mx(op, alg, FMI_F32, out.data(), nullptr, out.size(), ins, in_scales, rank, stream);
 }
+// With stochastic rounding (the output of the inputs' type: a float output has nothing to round).
+template <class A>
+inline void reduce_tree_mx(int op, int alg, Bucket<A>& out, Bucket<float8_e8m0>& out_scales, const std::vector<const Bucket<A>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank, fmi_stream_t stream, const Sr& sr) {
+    if (out_scales.size() != mx_blocks(out.size())) throw std::runtime_error("Dev::reduce_tree_mx: out_scales holds (n + 31) / 32 bytes");
+    detail::reduce_tree_mx(op, alg, dtype_of<A>(), out.data(), out_scales.data(), out.size(), ins, in_scales, rank, stream, &sr);
+}
 
 // float / Dev::half / Dev::bfloat16 data into an MX bucket and back (fmi_dev_mx_quantize / fmi_dev_mx_dequantize).
 template <class A, class S>
@@ -469,6 +495,28 @@ inline void mx_quantize(Bucket<A>& out, Bucket<float8_e8m0>& out_scales, const B
     static_assert(std::is_same_v<S, float> || std::is_same_v<S, half> || std::is_same_v<S, bfloat16>, "mx_quantize: float, Dev::half or Dev::bfloat16 source");
     if (out.size() != src.size() || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
     check(fmi_dev_mx_quantize(dtype_of<A>(), out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), stream), "fmi_dev_mx_quantize");
+}
+template <class A, class S>
+inline void mx_quantize(Bucket<A>& out, Bucket<float8_e8m0>& out_scales, const Bucket<S>& src, fmi_stream_t stream, const Sr& sr) {
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>, "mx_quantize: Dev::float8_e4m3 or Dev::float8_e5m2 elements");
+    static_assert(std::is_same_v<S, float> || std::is_same_v<S, half> || std::is_same_v<S, bfloat16>, "mx_quantize: float, Dev::half or Dev::bfloat16 source");
+    if (out.size() != src.size() || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
+    check(fmi_dev_mx_quantize_sr(dtype_of<A>(), out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), detail::sr_seed(sr), sr.first,
+                                 stream),
+          "fmi_dev_mx_quantize_sr");
+}
+// The same quantization of float values on the host (fmi_host_mx_quantize_sr; no device): `seed` is the value itself.
+template <class A>
+inline void mx_quantize_sr_host(std::vector<A>& out, std::vector<float8_e8m0>& out_scales, const std::vector<float>& src, std::uint64_t seed,
+                                std::uint64_t first = 0) {
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2> || std::is_same_v<A, float4_e2m1x2>,
+                  "mx_quantize_sr_host: Dev::float8_e4m3, Dev::float8_e5m2 or Dev::float4_e2m1x2 elements");
+    constexpr bool fp4 = std::is_same_v<A, float4_e2m1x2>;
+    out.assign(fp4 ? fp4_bytes(src.size()) : src.size(), A{});
+    out_scales.assign(mx_blocks(src.size()), float8_e8m0{});
+    int dtype = FMI_F4E2M1;
+    if constexpr (!fp4) dtype = dtype_of<A>();
+    check(fmi_host_mx_quantize_sr(dtype, out.data(), out_scales.data(), src.data(), src.size(), seed, first), "fmi_host_mx_quantize_sr");
 }
 template <class D, class A>
 inline void mx_dequantize(Bucket<D>& dst, const Bucket<A>& src, const Bucket<float8_e8m0>& src_scales, fmi_stream_t stream = nullptr) {
@@ -483,7 +531,8 @@ inline void mx_dequantize(Bucket<D>& dst, const Bucket<A>& src, const Bucket<flo
 namespace detail {
 inline void reduce_tree_mxfp4(int op, int alg, int out_dtype, void* out, void* out_scales, std::size_t n,
                               const std::vector<const Bucket<float4_e2m1x2>*>& ins,
-                              const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank, fmi_stream_t stream) {
+                              const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank, fmi_stream_t stream,
+                              const Sr* sr = nullptr) {
     if (ins.empty() || ins.size() > static_cast<std::size_t>(std::numeric_limits<int>::max()) || in_scales.size() != ins.size())
         throw std::runtime_error("Dev::reduce_tree_mx: need at least one input bucket and one scale bucket per input");
     std::vector<const void*> ptrs, sptrs;
@@ -493,6 +542,12 @@ inline void reduce_tree_mxfp4(int op, int alg, int out_dtype, void* out, void* o
             throw std::runtime_error("Dev::reduce_tree_mx: a scale bucket holds (n + 31) / 32 bytes");
         ptrs.push_back(ins[p]->data());
         sptrs.push_back(in_scales[p]->data());
+    }
+    if (sr) {
+        check(fmi_dev_reduce_tree_mx_sr(op, FMI_F4E2M1, alg, out, out_scales, ptrs.data(), sptrs.data(), sr_seed(*sr), sr->first,
+                                        static_cast<int>(ins.size()), rank, n, stream),
+              "fmi_dev_reduce_tree_mx_sr");
+        return;
     }
     check(fmi_dev_reduce_tree_mx(op, FMI_F4E2M1, alg, out_dtype, out, out_scales, ptrs.data(), sptrs.data(),
                                  static_cast<int>(ins.size()), rank, n, stream),
@@ -507,6 +562,13 @@ inline void reduce_tree_mx(int op, int alg, Bucket<float4_e2m1x2>& out, Bucket<f
         throw std::runtime_error("Dev::reduce_tree_mx: out holds (n + 1) / 2 bytes and out_scales (n + 31) / 32");
     detail::reduce_tree_mxfp4(op, alg, FMI_F4E2M1, out.data(), out_scales.data(), n, ins, in_scales, rank, stream);
 }
+inline void reduce_tree_mx(int op, int alg, Bucket<float4_e2m1x2>& out, Bucket<float8_e8m0>& out_scales, std::size_t n,
+                           const std::vector<const Bucket<float4_e2m1x2>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank, fmi_stream_t stream, const Sr& sr) {
+    if (out.size() != fp4_bytes(n) || out_scales.size() != mx_blocks(n))
+        throw std::runtime_error("Dev::reduce_tree_mx: out holds (n + 1) / 2 bytes and out_scales (n + 31) / 32");
+    detail::reduce_tree_mxfp4(op, alg, FMI_F4E2M1, out.data(), out_scales.data(), n, ins, in_scales, rank, stream, &sr);
+}
 inline void reduce_tree_mx(int op, int alg, Bucket<float>& out, std::size_t n, const std::vector<const Bucket<float4_e2m1x2>*>& ins,
                            const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank = 0, fmi_stream_t stream = nullptr) {
     if (out.size() != n) throw std::runtime_error("Dev::reduce_tree_mx: a float output holds n elements");
@@ -518,6 +580,14 @@ inline void mx_quantize(Bucket<float4_e2m1x2>& out, Bucket<float8_e8m0>& out_sca
     static_assert(std::is_same_v<S, float> || std::is_same_v<S, half> || std::is_same_v<S, bfloat16>, "mx_quantize: float, Dev::half or Dev::bfloat16 source");
     if (out.size() != fp4_bytes(src.size()) || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
     check(fmi_dev_mx_quantize(FMI_F4E2M1, out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), stream), "fmi_dev_mx_quantize");
+}
+template <class S>
+inline void mx_quantize(Bucket<float4_e2m1x2>& out, Bucket<float8_e8m0>& out_scales, const Bucket<S>& src, fmi_stream_t stream, const Sr& sr) {
+    static_assert(std::is_same_v<S, float> || std::is_same_v<S, half> || std::is_same_v<S, bfloat16>, "mx_quantize: float, Dev::half or Dev::bfloat16 source");
+    if (out.size() != fp4_bytes(src.size()) || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
+    check(fmi_dev_mx_quantize_sr(FMI_F4E2M1, out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), detail::sr_seed(sr), sr.first,
+                                 stream),
+          "fmi_dev_mx_quantize_sr");
 }
 template <class D>
 inline void mx_dequantize(Bucket<D>& dst, const Bucket<float4_e2m1x2>& src, const Bucket<float8_e8m0>& src_scales, fmi_stream_t stream = nullptr) {

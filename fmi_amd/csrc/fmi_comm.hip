@@ -1787,11 +1787,13 @@ int allreduce_scaled_device(Comm* c, int dtype, int alg, int out_dtype, const vo
 // fmi_comm_allreduce_mx (include/fmi_dev.h): allreduce_scaled_device over MX buckets. The scale bytes take the
 // elements' route on a grid of their own, shard / 32 bytes per shard (kShardAlign is 64 elements: every shard boundary
 // is a block boundary). The shard kernel runs on the shard's TRUE length, so a padded block is never computed.
+// seed != nullptr: fmi_comm_allreduce_mx_sr. Each owner rounds its shard at the stream position first + its shard's
+// offset in the bucket, so the gathered result is the single-device call's.
 int allreduce_mx_device(Comm* c, int op, int dtype, int alg, int out_dtype, const void* send, const void* send_scales,
-                        void* recv, void* recv_scales, size_t n, hipStream_t s) {
+                        void* recv, void* recv_scales, size_t n, hipStream_t s, const uint64_t* seed = nullptr, uint64_t first = 0) {
     const int N = c->t->n();
     if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE))  // the P = 1 form: not a copy
-        return reduce_tree_mx(op, dtype, alg, out_dtype, recv, recv_scales, &send, &send_scales, 1, 0, n, s);
+        return reduce_tree_mx(op, dtype, alg, out_dtype, recv, recv_scales, &send, &send_scales, 1, 0, n, s, seed, first);
     static_assert(kShardAlign % 32 == 0, "shard boundaries are MX block (and so FP4 byte) boundaries");
     const bool wide = out_dtype == FMI_F32;
     // Byte counts: eb per input shard (shard for the 8-bit floats; shard / 2 for FMI_F4E2M1, whole bytes and whole
@@ -1824,7 +1826,8 @@ int allreduce_mx_device(Comm* c, int op, int dtype, int alg, int out_dtype, cons
         std::vector<const void*> parts(N), sparts(N);
         for (int j = 0; j < N; ++j) parts[j] = staging + j * eb, sparts[j] = sstaging + j * sshard;
         FMI_COMM_RC(c->timing.begin(s));
-        FMI_COMM_RC(reduce_tree_mx(op, dtype, alg, out_dtype, red, sred, parts.data(), sparts.data(), N, 0, len, s));
+        FMI_COMM_RC(reduce_tree_mx(op, dtype, alg, out_dtype, red, sred, parts.data(), sparts.data(), N, 0, len, s, seed,
+                                   first + static_cast<uint64_t>(c->t->rank()) * shard));
         FMI_COMM_RC(c->timing.end(s));
     }
     if (!ragged) {
@@ -2105,12 +2108,19 @@ static int comm_allreduce_scaled_impl(fmi_comm_t comm, int op, int dtype_arg, in
     return allreduce_scaled_device(c, dtype, alg, out_dtype, send, in_scale, recv, out_scale, amax, n, resolve_stream(stream));
 }
 
+// sr: fmi_comm_allreduce_mx_sr (out_dtype is the storage dtype of dtype_arg; seed and first checked here).
 static int comm_allreduce_mx_impl(fmi_comm_t comm, int op, int dtype_arg, int alg, int out_dtype, const void* send,
-                                  const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream) {
+                                  const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream,
+                                  bool sr = false, const uint64_t* seed = nullptr, uint64_t first = 0) {
+    const char* who = sr ? "fmi_comm_allreduce_mx_sr" : "fmi_comm_allreduce_mx";
     int dtype = 0;
-    FMI_COMM_RC(mx_check_args("fmi_comm_allreduce_mx", op, dtype_arg, alg, out_dtype, recv_scales, &dtype));
+    FMI_COMM_RC(mx_check_args(who, op, dtype_arg, alg, sr ? storage_dtype(dtype_arg) : out_dtype, recv_scales, &dtype));
+    if (sr) {
+        out_dtype = dtype;
+        FMI_COMM_RC(mx_sr_check(who, seed, first, n));
+    }
     if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE_LTR)
-        return fail(FMI_ERR_INVALID, "fmi_comm_allreduce_mx: alg must be ALLREDUCE or REDUCE_LTR");
+        return fail(FMI_ERR_INVALID, std::string(who) + ": alg must be ALLREDUCE or REDUCE_LTR");
     if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
     if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
     if (static_cast<Comm*>(comm)->t->aborted()) return aborted_error();
@@ -2118,7 +2128,7 @@ static int comm_allreduce_mx_impl(fmi_comm_t comm, int op, int dtype_arg, int al
     if (!send || !recv || !send_scales) return fail(FMI_ERR_INVALID, "null bucket");
     Comm* c = static_cast<Comm*>(comm);
     std::lock_guard<std::mutex> lk(c->mu);
-    return allreduce_mx_device(c, op, dtype, alg, out_dtype, send, send_scales, recv, recv_scales, n, resolve_stream(stream));
+    return allreduce_mx_device(c, op, dtype, alg, out_dtype, send, send_scales, recv, recv_scales, n, resolve_stream(stream), seed, first);
 }
 
 // Three-stage pipeline over HostPipe::depth() chunk slots: while chunk k is allreduced on pipe.cs, chunk k+1 loads on
@@ -2431,6 +2441,13 @@ int fmi_comm_allreduce_mx(fmi_comm_t comm, int op, int dtype, int alg, int out_d
                           const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream) {
     return on_stream("fmi_comm_allreduce_mx", comm, stream, [&] {
         return comm_allreduce_mx_impl(comm, op, dtype, alg, out_dtype, send, send_scales, recv, recv_scales, n, stream);
+    });
+}
+
+int fmi_comm_allreduce_mx_sr(fmi_comm_t comm, int op, int dtype, int alg, const void* send, const void* send_scales, void* recv,
+                             void* recv_scales, size_t n, const uint64_t* seed, uint64_t first, fmi_stream_t stream) {
+    return on_stream("fmi_comm_allreduce_mx_sr", comm, stream, [&] {
+        return comm_allreduce_mx_impl(comm, op, dtype, alg, dtype, send, send_scales, recv, recv_scales, n, stream, true, seed, first);
     });
 }
 

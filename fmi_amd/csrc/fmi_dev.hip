@@ -1887,8 +1887,21 @@ static int mx_check_convert(const char* who, int dtype, const char* what, int wi
     return FMI_OK;
 }
 
+int mx_sr_check(const char* who, const void* seed, uint64_t first, size_t n) {
+    const std::string w = std::string(who) + ": ";
+    if (!seed) return fail(FMI_ERR_INVALID, w + "seed is NULL: stochastic rounding reads one u64 from device memory");
+    if (reinterpret_cast<uintptr_t>(seed) % 8 != 0)
+        return fail(FMI_ERR_INVALID, w + "seed is not 8-byte aligned: the kernels read the u64 with one load");
+    if (first % 32 != 0)
+        return fail(FMI_ERR_INVALID, w + "first " + std::to_string(first) + " is not a multiple of 32 (a call starts on an MX block)");
+    uint64_t end = 0;
+    if (__builtin_add_overflow(first, static_cast<uint64_t>(n), &end))
+        return fail(FMI_ERR_INVALID, w + "first + n wraps 2^64: the stream positions of one call do not");
+    return FMI_OK;
+}
+
 int reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* out_scales, const void* const* ins,
-                   const void* const* in_scales, int P, int rank, size_t n, hipStream_t s) {
+                   const void* const* in_scales, int P, int rank, size_t n, hipStream_t s, const uint64_t* seed, uint64_t first) {
     if (n == 0) return FMI_OK;
     const bool wide = out_dtype == FMI_F32;
     bool aligned = aligned16(out);
@@ -1906,6 +1919,7 @@ int reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* o
         ptrs.out[0] = out;
         mx.out_scales = static_cast<uint8_t*>(out_scales);
         mx.r = op == FMI_OP_AVG ? 1.0f / static_cast<float>(P) : 1.0f;
+        mx.seed = seed, mx.first = first;
         return launch_fused_mx(alg, dtype, out_dtype, P, ptrs, mx, n, s);
     }
     // Beyond the fused kernels: v_p into f32 temporaries (FMI_ACC_F32's allocation and lock), the library's own FMI_F32
@@ -1930,7 +1944,9 @@ int reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* o
         if (wide) S = static_cast<float*>(out);
         rc = reduce_tree_impl(op, FMI_F32, alg, S, fin.data(), P, rank, n, s);
     }
-    if (rc == FMI_OK && !wide) rc = launch_mx_quantize(dtype, out, static_cast<uint8_t*>(out_scales), FMI_F32, S, n, s);
+    if (rc == FMI_OK && !wide)
+        rc = seed ? launch_mx_quantize_sr(dtype, out, static_cast<uint8_t*>(out_scales), FMI_F32, S, n, seed, first, s)
+                  : launch_mx_quantize(dtype, out, static_cast<uint8_t*>(out_scales), FMI_F32, S, n, s);
     FMI_HIP_TRY(hipEventRecord(g_acc.free, s));
     return rc;
 }
@@ -1959,6 +1975,45 @@ int fmi_dev_mx_quantize(int dtype, void* out, void* out_scales, int src_dtype, c
         if (!out || !out_scales || !src) return fail(FMI_ERR_INVALID, "fmi_dev_mx_quantize: null buffer (out, out_scales or src)");
         if (int rc = require_device()) return rc;
         return launch_mx_quantize(dtype, out, static_cast<uint8_t*>(out_scales), src_dtype, src, n, resolve(stream));
+    });
+}
+
+int fmi_dev_reduce_tree_mx_sr(int op, int dtype_arg, int alg, void* out, void* out_scales, const void* const* ins,
+                              const void* const* in_scales, const uint64_t* seed, uint64_t first, int P, int rank, size_t n,
+                              fmi_stream_t stream) {
+    return guarded("fmi_dev_reduce_tree_mx_sr", [&]() -> int {
+        int dtype = storage_dtype(dtype_arg);
+        if (int rc = mx_check_args("fmi_dev_reduce_tree_mx_sr", op, dtype_arg, alg, dtype, out_scales, &dtype)) return rc;
+        if (int rc = mx_sr_check("fmi_dev_reduce_tree_mx_sr", seed, first, n)) return rc;
+        if (int rc = check_peer_count(P)) return rc;  // op and dtype: mx_check_args above
+        if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
+        if (!out || !ins || !in_scales) return fail(FMI_ERR_INVALID, "null buffer");
+        for (int p = 0; p < P; ++p)
+            if (!ins[p] || !in_scales[p]) return fail(FMI_ERR_INVALID, "null input bucket or scale array");
+        if (int rc = require_device()) return rc;
+        return reduce_tree_mx(op, dtype, alg, dtype, out, out_scales, ins, in_scales, P, rank, n, resolve(stream), seed, first);
+    });
+}
+
+int fmi_dev_mx_quantize_sr(int dtype, void* out, void* out_scales, int src_dtype, const void* src, size_t n, const uint64_t* seed,
+                           uint64_t first, fmi_stream_t stream) {
+    return guarded("fmi_dev_mx_quantize_sr", [&]() -> int {
+        if (int rc = mx_check_convert("fmi_dev_mx_quantize_sr", dtype, "src_dtype", src_dtype)) return rc;
+        if (int rc = mx_sr_check("fmi_dev_mx_quantize_sr", seed, first, n)) return rc;
+        if (n == 0) return FMI_OK;
+        if (!out || !out_scales || !src) return fail(FMI_ERR_INVALID, "fmi_dev_mx_quantize_sr: null buffer (out, out_scales or src)");
+        if (int rc = require_device()) return rc;
+        return launch_mx_quantize_sr(dtype, out, static_cast<uint8_t*>(out_scales), src_dtype, src, n, seed, first, resolve(stream));
+    });
+}
+
+int fmi_host_mx_quantize_sr(int dtype, void* out, void* out_scales, const float* src, size_t n, uint64_t seed, uint64_t first) {
+    return guarded("fmi_host_mx_quantize_sr", [&]() -> int {
+        if (int rc = mx_check_convert("fmi_host_mx_quantize_sr", dtype, "src_dtype", FMI_F32)) return rc;
+        if (int rc = mx_sr_check("fmi_host_mx_quantize_sr", &seed, first, n)) return rc;
+        if (n == 0) return FMI_OK;
+        if (!out || !out_scales || !src) return fail(FMI_ERR_INVALID, "fmi_host_mx_quantize_sr: null buffer (out, out_scales or src)");
+        return host_mx_quantize_sr(dtype, out, static_cast<uint8_t*>(out_scales), src, n, seed, first);
     });
 }
 

@@ -255,11 +255,15 @@ int reduce_tree_scaled(int dtype, int alg, int out_dtype, void* out, const void*
 // fmi_dev_reduce_tree_mx (include/fmi_dev.h): the sum or mean of block-scaled (MX) 8-bit float buckets. What its fused
 // kernels take beside the peer pointers, the kernel argument's 2 P + 2 pointers in all: in_scales[t] the E8M0 scale
 // bytes of ptrs.in[t] (a kReduce call's caller rotates them with the inputs), out_scales the result's (unused with an
-// f32 output), r the mean's factor fl32(1 / P), or 1.0f for a sum.
+// f32 output), r the mean's factor fl32(1 / P), or 1.0f for a sum. seed / first: the stochastic-rounding calls alone
+// (fmi_dev_reduce_tree_mx_sr): the device word that holds the Philox key and the stream position of element 0, a
+// multiple of 32; seed == nullptr is a round-to-nearest call, whose kernels read neither.
 struct MxArgs {
     const uint8_t* in_scales[sched::kMaxFusedPeers];
     uint8_t* out_scales;
     float r;
+    const uint64_t* seed;
+    uint64_t first;
 };
 // The fused MX kernels (fmi_fused.hip -> fmi_fused_mx_*.hip): 2 <= P <= 16, the element buckets 16-B aligned, the
 // scale arrays of any alignment. alg, dtype, out_dtype, ptrs as launch_fused_scaled's.
@@ -274,16 +278,35 @@ MxUnit mx_unit;
 using Mxfp4Unit = int(int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
 template <int ALG>
 Mxfp4Unit mxfp4_unit;
+// The stochastic-rounding kernels of the same two families (mx.seed != nullptr; the element type's own output only):
+// defined in fmi_mx_sr_impl.h / fmi_mxfp4_sr_impl.h, instantiated by one fmi_fused_mx_sr_*.hip /
+// fmi_fused_mxfp4_sr_*.hip each. launch_fused_mx sends a call with a seed here.
+using MxSrUnit = int(int dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
+template <int ALG>
+MxSrUnit mx_sr_unit;
+using Mxfp4SrUnit = int(int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
+template <int ALG>
+Mxfp4SrUnit mxfp4_sr_unit;
 // fmi_dev_mx_dequantize / fmi_dev_mx_quantize (fmi_mx.hip), any alignment, one launch each. dtype: FMI_F8E4M3,
 // FMI_F8E5M2 or FMI_F4E2M1 (packed: n elements in ceil(n / 2) bytes); dst_dtype / src_dtype: FMI_F32, FMI_F16 or FMI_BF16 (FMI_ERR_INVALID otherwise).
 int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s);
 int launch_mx_quantize(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s);
+// fmi_dev_mx_quantize_sr: launch_mx_quantize with narrow_sr (fmi_mx_sr.h); seed one u64 in device memory, first the
+// stream position of element 0 (a multiple of 32).
+int launch_mx_quantize_sr(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, const uint64_t* seed,
+                          uint64_t first, hipStream_t s);
+// fmi_host_mx_quantize_sr after its checks (fmi_mx_sr.hip): the same quantization on host memory, from the same functions.
+int host_mx_quantize_sr(int dtype, void* out, uint8_t* out_scales, const float* src, size_t n, uint64_t seed, uint64_t first);
 // The host-side checks of fmi_dev_reduce_tree_mx's op, dtype argument, alg, out_dtype and out_scales (fmi_dev.hip),
 // shared with fmi_comm_allreduce_mx; *dtype: the storage dtype. And the call after its validation: the comm call's
 // shard step.
 int mx_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype, const void* out_scales, int* dtype);
+// seed != nullptr: the stochastic-rounding call (out_dtype == dtype), element 0 at stream position `first`.
 int reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* out_scales, const void* const* ins,
-                   const void* const* in_scales, int P, int rank, size_t n, hipStream_t s);
+                   const void* const* in_scales, int P, int rank, size_t n, hipStream_t s, const uint64_t* seed = nullptr,
+                   uint64_t first = 0);
+// The host-side checks the stochastic-rounding calls add: seed, first % 32, first + n.
+int mx_sr_check(const char* who, const void* seed, uint64_t first, size_t n);
 // kReducePartials for any P and any alignment / dtype (fused kernel where it applies, pairwise passes otherwise):
 // outs[t] = the value transformed peer t of reduce_no_order holds in its sendbuf at the end
 // (src/comm/PeerToPeer.cpp:66-78); ins in transformed order. Defined in fmi_dev.hip.

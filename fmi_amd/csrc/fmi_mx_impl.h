@@ -37,7 +37,7 @@ __device__ __forceinline__ uint32_t mx_abs_bits(float f) { return __builtin_bit_
 // The scale byte of a block whose largest |S| has the bits A: 255 where the block holds an inf or a NaN; otherwise the
 // smallest power of two that brings A to at most the largest finite element, 1.75 * 2^EMAX (mantissa bits 0x600000).
 template <class T>
-__device__ __forceinline__ uint32_t mx_scale_byte(uint32_t A) {
+__host__ __device__ __forceinline__ uint32_t mx_scale_byte(uint32_t A) {
     constexpr int kEmax = std::is_same_v<T, f8e5m2> ? 15 : 8;
     const int f = static_cast<int>(A >> 23);
     const int e = f - kEmax + ((A & 0x7FFFFFu) > 0x600000u ? 1 : 0);

@@ -493,15 +493,30 @@ def _mx_elements(who: str, what: str, b: Bucket) -> DType:
     return b.dtype
 
 
+def _sr_seed(who: str, seed, out: Bucket, first: int) -> int:
+    """The device word of a stochastic-rounding call: a U64 bucket of one element."""
+    if not isinstance(seed, Bucket) or seed.dtype != DType.U64 or seed.n != 1:
+        raise ValueError(f"{who}: `seed` must be a U64 bucket of one element (the Philox key, in device memory)")
+    if out.dtype == DType.F32:
+        raise ValueError(f"{who}: stochastic rounding needs an output of the element type: an F32 output has nothing to round")
+    if not 0 <= int(first) < 1 << 64:
+        raise ValueError(f"{who}: `first` must be an unsigned 64-bit stream position")
+    return seed.ptr
+
+
 def reduce_tree_mx(op: Op, alg: Alg, out: Bucket, out_scales: Optional[Bucket], ins: Sequence[Bucket],
-                   in_scales: Sequence[Bucket], rank: int = 0, stream=None) -> None:
+                   in_scales: Sequence[Bucket], rank: int = 0, stream=None, seed: Optional[Bucket] = None,
+                   first: int = 0) -> None:
     """The sum (Op.SUM) or mean (Op.AVG) of block-scaled (MX) F8E4M3 / F8E5M2 (MXFP8) or F4E2M1 (MXFP4, packed two
     elements to a byte; the scale rule at EMAX = 2) buckets (fmi_dev_reduce_tree_mx): every
     input element times its block's E8M0 scale in f32, the f32 SUM program of `alg`, then either stored as F32 (`out` an
     F32 bucket, out_scales None) or requantized: per block of 32 the smallest power-of-two scale that brings the block's
     largest magnitude within the element type, into `out_scales`, and the scaled sum narrowed into `out`. in_scales[p]
     and out_scales are F8E8M0 buckets of ceil(n / 32) bytes. One fused kernel at 2..16 peers on 16-B aligned element
-    buckets; bit-exact and deterministic."""
+    buckets; bit-exact and deterministic.
+    seed: a U64 bucket of one element selects stochastic rounding (fmi_dev_reduce_tree_mx_sr): the same scale bytes, every
+    element rounded to one of its two grid neighbours by 16 Philox bits keyed by (the word in `seed`, first + its index).
+    `first`, a multiple of 32, is the stream position of element 0: a bucket reduced in pieces passes each piece's offset."""
     if not ins:
         raise ValueError("need at least one peer bucket")
     dtype = _mx_elements("reduce_tree_mx", "input buckets", ins[0])
@@ -513,19 +528,47 @@ def reduce_tree_mx(op: Op, alg: Alg, out: Bucket, out_scales: Optional[Bucket], 
     if out.dtype != DType.F32 and out_scales is None:
         raise ValueError("reduce_tree_mx: out_scales is missing: only an F32 output has no scale bytes")
     sptrs = (ctypes.c_void_p * len(ins))(*[_mx_scales(b, f"in_scales[{p}]", out.n) for p, b in enumerate(in_scales)])
+    if seed is not None:
+        word = _sr_seed("reduce_tree_mx", seed, out, first)
+        _lib.call("fmi_dev_reduce_tree_mx_sr", int(op), int(dtype), int(alg), out.ptr, _mx_scales(out_scales, "out_scales", out.n),
+                  _ptr_array(ins), sptrs, word, int(first), len(ins), rank, out.n, _sptr(stream))
+        return
     _lib.call("fmi_dev_reduce_tree_mx", int(op), int(dtype), int(alg), int(out.dtype), out.ptr,
               None if out_scales is None else _mx_scales(out_scales, "out_scales", out.n), _ptr_array(ins), sptrs,
               len(ins), rank, out.n, _sptr(stream))
 
 
-def mx_quantize(out: Bucket, out_scales: Bucket, src: Bucket, stream=None) -> None:
+def mx_quantize(out: Bucket, out_scales: Bucket, src: Bucket, stream=None, seed: Optional[Bucket] = None, first: int = 0) -> None:
     """An F32 / F16 / BF16 bucket into an MX bucket (fmi_dev_mx_quantize): per block of 32 elements the scale byte of
-    reduce_tree_mx, into `out_scales`, and the elements narrowed under it into `out` (F8E4M3 / F8E5M2)."""
+    reduce_tree_mx, into `out_scales`, and the elements narrowed under it into `out` (F8E4M3 / F8E5M2). seed, first: as
+    reduce_tree_mx's (fmi_dev_mx_quantize_sr)."""
     dtype = _mx_elements("mx_quantize", "output bucket", out)
     if src.dtype not in (DType.F32, DType.F16, DType.BF16) or src.n != out.n:
         raise ValueError("mx_quantize: `src` must be an F32, F16 or BF16 bucket of out's length")
+    if seed is not None:
+        _lib.call("fmi_dev_mx_quantize_sr", int(dtype), out.ptr, _mx_scales(out_scales, "out_scales", out.n), int(src.dtype),
+                  src.ptr, out.n, _sr_seed("mx_quantize", seed, out, first), int(first), _sptr(stream))
+        return
     _lib.call("fmi_dev_mx_quantize", int(dtype), out.ptr, _mx_scales(out_scales, "out_scales", out.n), int(src.dtype),
               src.ptr, out.n, _sptr(stream))
+
+
+def mx_quantize_sr_host(dtype, src, seed: int, first: int = 0):
+    """fmi_dev_mx_quantize_sr of a float32 numpy array on the host (fmi_host_mx_quantize_sr): (element bytes, scale bytes)
+    as np.uint8 arrays, the bytes the device call stores for the same (seed, first). dtype: F8E4M3, F8E5M2 or F4E2M1
+    (packed, ceil(n / 2) bytes). Needs no device."""
+    dtype = DType(dtype)
+    if dtype not in (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1):
+        raise ValueError(f"mx_quantize_sr_host needs F8E4M3, F8E5M2 or F4E2M1, got {dtype.name}")
+    a = np.ascontiguousarray(src, np.float32).ravel()
+    n = a.size
+    out = np.zeros((n + 1) // 2 if dtype == DType.F4E2M1 else n, np.uint8)
+    scales = np.zeros(mx_blocks(n), np.uint8)
+    if not 0 <= int(seed) < 1 << 64 or not 0 <= int(first) < 1 << 64:
+        raise ValueError("mx_quantize_sr_host: seed and first are unsigned 64-bit values")
+    _lib.call("fmi_host_mx_quantize_sr", int(dtype), out.ctypes.data, scales.ctypes.data,
+              a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), n, int(seed), int(first))
+    return out, scales
 
 
 def mx_dequantize(dst: Bucket, src: Bucket, src_scales: Bucket, stream=None) -> None:

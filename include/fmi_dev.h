@@ -437,6 +437,48 @@ int fmi_dev_reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out,
 int fmi_dev_mx_quantize(int dtype, void* out, void* out_scales, int src_dtype, const void* src, size_t n, fmi_stream_t stream);
 int fmi_dev_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const void* src_scales, size_t n, fmi_stream_t stream);
 
+/* Stochastic rounding (SR) for the MX calls: fmi_dev_reduce_tree_mx with out_dtype == dtype, and fmi_dev_mx_quantize,
+ * with the last step alone changed. v_p, the f32 program S, the mean's r_P, the block's scale byte e_out (so every scale
+ * byte equals the round-to-nearest call's) and y = fl32(S * 2^(127 - e_out)) are as defined above; narrow(y) becomes
+ * narrow_sr(y, r), r a 16-bit random integer that belongs to the ELEMENT, a pure function of (seed, stream position):
+ *     element i of the output has the stream position j = first + i (u64);  q = j >> 3
+ *     (W0, W1, W2, W3) = Philox4x32-10( counter (q & 0xFFFFFFFF, q >> 32, 0, 0), key (seed & 0xFFFFFFFF, seed >> 32) )
+ *         one round: (c0, c1, c2, c3) <- ( hi32(M1 c2) ^ c1 ^ k0, lo32(M1 c2), hi32(M0 c0) ^ c3 ^ k1, lo32(M0 c0) ), then
+ *         k0 += 0x9E3779B9, k1 += 0xBB67AE85;  M0 = 0xD2511F53, M1 = 0xCD9E8D57;  ten rounds
+ *         (counter 0, key 0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8)
+ *     r = ( W[(j & 7) >> 1] >> (16 * (j & 1)) ) & 0xFFFF            one Philox call serves 8 consecutive elements
+ * narrow_sr, for the finite |y| <= the largest finite element that the scale rule guarantees (SR cannot overflow): G the
+ * ascending non-negative finite magnitudes of the type (E2M1: 8; E4M3: codes 0x00..0x7E; E5M2: codes 0x00..0x7B);
+ *     lo = max{ g in G : g <= |y| };  |y| == lo: the magnitude is lo, whatever the seed (a grid value never moves);
+ *     otherwise hi = the next element of G, T = 65536 (|y| - lo) / (hi - lo)  (exact), and the magnitude is hi if
+ *     r + 0.5 < T, else lo.  The code's sign bit is y's, -0 included.
+ * So P(up) = round(T) / 65536 and the expectation lies within 2^-17 of a grid step of |y|. A block with e_out == 255
+ * stores what the round-to-nearest call stores (0x7F bytes, zero nibbles). An equal form in integers: with (M, EMIN) =
+ * (1, 0) for E2M1, (3, -6) for E4M3, (2, -14) for E5M2, e the unbiased exponent of |y| (-126 for a subnormal) and sig its
+ * 24-bit significand (no implicit bit for a subnormal):
+ *     d = 23 - M + max(EMIN - e, 0);  D = sig mod 2^d;  up = ((2 r + 1) << (d - 17)) < D  (never once d - 17 >= 24);
+ *     the result's significand is (sig >> d) + up at the exponent max(e, EMIN).
+ * The result does not depend on the access policy, the grid, the fused / fallback route, or on how a bucket is split
+ * between calls at multiples of 32 elements (the second call passes first + the elements before it).
+ * fmi_dev_reduce_tree_mx_sr: fmi_dev_reduce_tree_mx's dtypes, ops, algs, P, rank and aliasing rules, the output of the
+ * input's dtype (an f32 output has nothing to round). seed: ONE u64 in DEVICE memory, 8-byte aligned (the kernels read
+ * it with one load), so a captured graph replays with whatever the word then holds and nobody synchronises; first: a
+ * host value. FMI_ERR_INVALID on the host, before a device is needed: seed == NULL or not 8-byte aligned, first % 32 != 0,
+ * first + n wrapping 2^64, and everything the round-to-nearest call refuses. n = 0 succeeds. 2 <= P <= 16 with 16-B
+ * aligned element buckets: one fused kernel, graph-capturable; any other call runs dequantize, the f32 program and
+ * fmi_dev_mx_quantize_sr at the same `first`.
+ * fmi_dev_mx_quantize_sr: fmi_dev_mx_quantize with narrow_sr; the same checks. Additive: fmi_abi_version() stays 1. */
+int fmi_dev_reduce_tree_mx_sr(int op, int dtype, int alg, void* out, void* out_scales, const void* const* ins,
+                              const void* const* in_scales, const uint64_t* seed, uint64_t first, int P, int rank, size_t n,
+                              fmi_stream_t stream);
+int fmi_dev_mx_quantize_sr(int dtype, void* out, void* out_scales, int src_dtype, const void* src, size_t n, const uint64_t* seed,
+                           uint64_t first, fmi_stream_t stream);
+/* fmi_dev_mx_quantize_sr from FMI_F32 on HOST memory, in plain C++ from the functions the kernels use: the same bytes.
+ * `seed` is the value itself. Needs no device: a CPU check of the definition above. dtype, first and n are checked as
+ * there; out holds n bytes (FMI_F4E2M1: ceil(n / 2), an odd bucket's last high nibble written 0), out_scales
+ * ceil(n / 32). */
+int fmi_host_mx_quantize_sr(int dtype, void* out, void* out_scales, const float* src, size_t n, uint64_t seed, uint64_t first);
+
 /* Peer-axis inclusive scan of P device buckets: outs[k] = x0 (+) ... (+) xk with the evaluation order
  * of `alg` (FMI_ALG_SCAN or FMI_ALG_SCAN_LTR). Replaces reference PeerToPeer::scan_no_order / scan_ltr
  * (src/comm/PeerToPeer.cpp:154-184, :141-152) and Communicator::scan (include/Communicator.h:135-150)
@@ -561,6 +603,14 @@ int fmi_comm_allreduce_scaled(fmi_comm_t comm, int op, int dtype, int alg, int o
  * last non-empty shard can have an odd true length. */
 int fmi_comm_allreduce_mx(fmi_comm_t comm, int op, int dtype, int alg, int out_dtype, const void* send,
                           const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream);
+/* fmi_comm_allreduce_mx with stochastic rounding (fmi_dev_reduce_tree_mx_sr above): the same route, the output of the
+ * input's dtype. Each owner runs the device call on its shard at first + the shard's offset in the bucket (shards are
+ * multiples of 64 elements, so that stays a multiple of 32). Every rank must hold the same value in its device word
+ * `seed` and pass the same `first`; every rank's recv / recv_scales is then the single-device call over the ranks'
+ * buckets at (seed, first). seed == NULL or misaligned, first % 32 != 0 and first + n wrapping 2^64 are FMI_ERR_INVALID, checked with
+ * the other arguments before a device is needed. */
+int fmi_comm_allreduce_mx_sr(fmi_comm_t comm, int op, int dtype, int alg, const void* send, const void* send_scales, void* recv,
+                             void* recv_scales, size_t n, const uint64_t* seed, uint64_t first, fmi_stream_t stream);
 /* Host-ingress allreduce (BASELINE config C5): `send` / `recv` are HOST buckets, i.e. the channel recv
  * buffers FMI's transports deliver into (reference src/comm/Direct.cpp:36-45, PeerToPeer.cpp:110-129).
  * The bucket streams through the GPU in chunks of `chunk` elements (0 = FMI_TUNE_HOST_CHUNK bytes):

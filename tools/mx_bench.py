@@ -28,6 +28,20 @@ kernel as the yardstick, in the same passes and at the same ELEMENT count (so th
 Bytes with the scale bytes counted: inputs P * (n / 2 + n / 32), output n / 2 + n / 32 or 4 n.
 
     python3 tools/mx_bench.py --kind e2m1 [--label NAME] [--out profiles/mxfp4_bench.jsonl]
+
+--sr: the stochastic-rounding kernels (fmi_dev_reduce_tree_mx_sr) beside the round-to-nearest ones, whose code is
+unchanged, in the same passes at the same element count:
+
+  mx                          reduce_tree_mx on E4M3 buckets, out = E4M3 (yardstick of mx_sr)
+  mxfp4                       reduce_tree_mx on F4E2M1 buckets, out = F4E2M1 (yardstick of mxfp4_sr)
+  mx_sr, mxfp4_sr             the same calls with a seed: the fused stochastic-rounding kernels
+  mx_f32_then_quantize_sr,    the fused kernel of the same element type with an F32 output, then mx_quantize with the
+  mxfp4_f32_then_quantize_sr  seed: the only way to stochastic rounding without the fused variant (8 n more bytes per call)
+
+Each row carries its element rate per pass and the ratio to its yardstick; the two fused rows also carry the ratio to the
+two-kernel composition of their own element type per pass and whether it exceeds 1 in every pass.
+
+    python3 tools/mx_bench.py --sr [--label NAME] [--out profiles/mx_sr_bench.jsonl]
 """
 import argparse
 import os
@@ -110,6 +124,84 @@ def main_e2m1(args):
     fmi_amd.sync()
 
 
+SR_ROWS = ("mx", "mxfp4", "mx_sr", "mxfp4_sr", "mx_f32_then_quantize_sr", "mxfp4_f32_then_quantize_sr")
+SR_YARDSTICK = {"mx": "mx", "mxfp4": "mxfp4", "mx_sr": "mx", "mxfp4_sr": "mxfp4", "mx_f32_then_quantize_sr": "mx",
+                "mxfp4_f32_then_quantize_sr": "mxfp4"}
+SR_COMPOSITION = {"mx_sr": "mx_f32_then_quantize_sr", "mxfp4_sr": "mxfp4_f32_then_quantize_sr"}
+
+
+def main_sr(args):
+    """n ELEMENTS per peer, as main_e2m1: E4M3 buckets of n bytes, F4E2M1 buckets of n / 2 bytes."""
+    P, n, S = args.peers, args.mib * MIB, args.sets
+    nb = fmi_amd.mx_blocks(n)
+    g8 = [Bucket.group(P + 1, n, DType.F8E4M3) for _ in range(S)]
+    g4 = [Bucket.group(P + 1, n, DType.F4E2M1) for _ in range(S)]
+    wide = [Bucket(n, np.float32) for _ in range(S)]
+    seed = Bucket.from_numpy(np.array([0x0123456789ABCDEF], np.uint64))
+    rng = np.random.default_rng(3)
+    packed = rng.integers(0, 256, n // 2, dtype=np.uint8)
+    scale_sets = []
+    for k in range(S):
+        for p in range(P):
+            g8[k][p].fill_synthetic(11, p)
+            g4[k][p].upload(packed ^ np.uint8(17 * (k * P + p) & 0xFF))
+        scale_sets.append([Bucket(nb, DType.F8E8M0) for _ in range(P + 1)])
+        for b in scale_sets[-1][:P]:
+            b.upload(rng.integers(120, 135, nb).astype(np.uint8))
+    fmi_amd.sync()
+
+    def tree(g, k, out=None, **kw):
+        s = scale_sets[k % S]
+        fmi_amd.reduce_tree_mx(Op.SUM, Alg.ALLREDUCE, g[k % S][P] if out is None else out, s[P] if out is None else None, g[k % S][:P], s[:P], **kw)
+
+    def composition(g):
+        def launch(k):
+            tree(g, k, out=wide[k % S])
+            fmi_amd.mx_quantize(g[k % S][P], scale_sets[k % S][P], wide[k % S], seed=seed, first=0)
+        return launch
+
+    launches = {
+        "mx": lambda k: tree(g8, k),
+        "mxfp4": lambda k: tree(g4, k),
+        "mx_sr": lambda k: tree(g8, k, seed=seed, first=0),
+        "mxfp4_sr": lambda k: tree(g4, k, seed=seed, first=0),
+        "mx_f32_then_quantize_sr": composition(g8),
+        "mxfp4_f32_then_quantize_sr": composition(g4),
+    }
+    in8, in4, out8, out4 = P * (n + nb), P * (n // 2 + nb), n + nb, n // 2 + nb
+    algo = {"mx": in8 + out8, "mx_sr": in8 + out8, "mxfp4": in4 + out4, "mxfp4_sr": in4 + out4,
+            "mx_f32_then_quantize_sr": in8 + 8 * n + out8, "mxfp4_f32_then_quantize_sr": in4 + 8 * n + out4}
+    ms = {r: [] for r in SR_ROWS}
+    for _ in range(PASSES):
+        for r in SR_ROWS:
+            ms[r].append(timed(launches[r], args.iters, S))
+    spread = lambda xs: round((max(xs) - min(xs)) / statistics.median(xs), 4)  # noqa: E731
+    elem = {r: [n / (m * 1e-3) for m in ms[r]] for r in SR_ROWS}
+    lines = []
+    for r in SR_ROWS:
+        byte_rate = [algo[r] / (m * 1e-3) for m in ms[r]]
+        ratios = [a / b for a, b in zip(elem[r], elem[SR_YARDSTICK[r]])]
+        line = {"tool": "tools/mx_bench.py --sr", "label": args.label, "inflight_kib": fmi_amd.tune_get(fmi_amd.Tune.FUSED_INFLIGHT_KIB),
+                "kernel": f"tree{P} {'e4m3' if SR_YARDSTICK[r] == 'mx' else 'e2m1'} {r}", "elements_per_peer": n, "algorithmic_bytes": algo[r],
+                "bytes_per_element": round(algo[r] / n, 4), "iters_per_pass": args.iters, "passes": PASSES, "rotating_sets": S,
+                "ms_per_pass": [round(m, 4) for m in ms[r]], "Gelem_s_per_pass": [round(x / 1e9, 2) for x in elem[r]],
+                "Gelem_s": round(statistics.median(elem[r]) / 1e9, 2), "GB_s_per_pass": [round(x / 1e9, 1) for x in byte_rate],
+                "GB_s": round(statistics.median(byte_rate) / 1e9, 1), "fraction_of_8TBs": round(statistics.median(byte_rate) / PEAK, 4),
+                "spread": spread(byte_rate), "yardstick": f"tree{P} {SR_YARDSTICK[r]} (round to nearest, code unchanged), same passes, element rate",
+                "element_rate_ratio_to_rne_per_pass": [round(x, 4) for x in ratios], "element_rate_ratio_to_rne": round(statistics.median(ratios), 4),
+                "timing": "two HIP events around back-to-back launches on the library stream"}
+        if r in SR_COMPOSITION:
+            over = [a / b for a, b in zip(elem[r], elem[SR_COMPOSITION[r]])]
+            line["composition"] = SR_COMPOSITION[r]
+            line["element_rate_ratio_to_composition_per_pass"] = [round(x, 4) for x in over]
+            line["exceeds_composition_in_every_pass"] = all(x > 1.0 for x in over)
+        lines.append(line)
+    emit(lines, args.out)
+    for b in [b for g in g8 + g4 for b in g] + wide + [b for s in scale_sets for b in s] + [seed]:
+        b.free()
+    fmi_amd.sync()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", default="e4m3", choices=("e4m3", "e5m2", "e2m1"))
@@ -121,8 +213,11 @@ def main():
     ap.add_argument("--rows", default=",".join(ROWS), help="which rows to run; the yardstick always runs")
     ap.add_argument("--label", default="tree")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--sr", action="store_true", help="the stochastic-rounding rows beside the round-to-nearest kernels")
     args = ap.parse_args()
     fmi_amd.init(0)
+    if args.sr:
+        return main_sr(args)
     if args.kind == "e2m1":
         if args.rows == ",".join(ROWS):
             args.rows = ",".join(FP4_ROWS)
