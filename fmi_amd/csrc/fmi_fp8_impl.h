@@ -57,6 +57,25 @@ __device__ __forceinline__ void fp8_narrow_half(Fp8Words& out, const Fp8Half& v)
     out.w[2 * H + 1] = fp8_narrow2<T, true>(v.p[3].x, v.p[3].y, fp8_narrow2<T, false>(v.p[2].x, v.p[2].y, 0u));
 }
 
+// A lane group's 16 f32 results, 64 B, with the output's own addressing (tile base and lane offset are 4x the input's):
+// the f32 output of the scaled and the MX kernels. POL, group0, lane: as Fp8Access's tile and lane.
+template <bool POL>
+__device__ __forceinline__ void fp8_store_f32(void* out, size_t group0, unsigned lane, const Fp8Half& lo, const Fp8Half& hi) {
+    Lanes<float, 4> q[4];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        q[k].v[0] = lo.p[2 * k].x, q[k].v[1] = lo.p[2 * k].y, q[k].v[2] = lo.p[2 * k + 1].x, q[k].v[3] = lo.p[2 * k + 1].y;
+        q[2 + k].v[0] = hi.p[2 * k].x, q[2 + k].v[1] = hi.p[2 * k].y, q[2 + k].v[2] = hi.p[2 * k + 1].x, q[2 + k].v[3] = hi.p[2 * k + 1].y;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if constexpr (POL)
+            store_tile<kTreeStoreAux, float, 4>(out, group0 * 64, lane * 64u + k * 16u, q[k]);
+        else
+            store_lanes<kFusedNT, float, 4>(static_cast<float*>(out) + (group0 + lane) * 16 + k * 4, q[k]);
+    }
+}
+
 template <class Op>
 __device__ __forceinline__ Fp8Half fp8_combine_half(const Fp8Half& a, const Fp8Half& b) {
     Fp8Half r;

@@ -81,20 +81,7 @@ __device__ __forceinline__ void scaled_group(const PeerPtrs& ptrs, size_t group0
     const Fp8Half lo = scaled_half<T, ALG, P, 0>(raw, s, t, want_amax, m);
     const Fp8Half hi = scaled_half<T, ALG, P, 1>(raw, s, t, want_amax, m);
     if constexpr (OUT32) {
-        // 16 f32 values, 64 B: the output's own addressing (tile base and lane offset are 4x the input's)
-        Lanes<float, 4> q[4];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            q[k].v[0] = lo.p[2 * k].x, q[k].v[1] = lo.p[2 * k].y, q[k].v[2] = lo.p[2 * k + 1].x, q[k].v[3] = lo.p[2 * k + 1].y;
-            q[2 + k].v[0] = hi.p[2 * k].x, q[2 + k].v[1] = hi.p[2 * k].y, q[2 + k].v[2] = hi.p[2 * k + 1].x, q[2 + k].v[3] = hi.p[2 * k + 1].y;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if constexpr (POL)
-                store_tile<kTreeStoreAux, float, 4>(ptrs.out[0], group0 * 64, lane * 64u + k * 16u, q[k]);
-            else
-                store_lanes<kFusedNT, float, 4>(static_cast<float*>(ptrs.out[0]) + (group0 + lane) * 16 + k * 4, q[k]);
-        }
+        fp8_store_f32<POL>(ptrs.out[0], group0, lane, lo, hi);
     } else {
         Fp8Words out;
         fp8_narrow_half<T, 0>(out, lo);

@@ -17,8 +17,8 @@
 //   MXFP4 sums and means     fmi_fused_mxfp4_*.hip, one per reduce algorithm (the same call at FMI_F4E2M1: E2M1 and f32
 //                            output; launch_fused_mx too)
 //   stochastic rounding      fmi_fused_mx_sr_*.hip and fmi_fused_mxfp4_sr_*.hip, one per reduce algorithm
-//                            (fmi_dev_reduce_tree_mx_sr: the same programs, the element type's output rounded by
-//                            narrow_sr; launch_fused_mx with a seed)
+//                            (fmi_dev_reduce_tree_mx_sr: the same kernels' SR instantiations, the element type's output
+//                            rounded by narrow_sr; launch_fused_mx with a seed)
 // Everything else a call can be runs elsewhere (fmi_dev.hip): P beyond a variant's kernels and unaligned buckets as
 // blocks of fused programs, as widen / the f32 program / narrow, as the SUM program and the scale kernel
 // (fmi_scale.hip), or as pairwise passes in the program's order.
@@ -139,32 +139,23 @@ int launch_fused_scaled(int alg, int dtype, int out_dtype, int P, const PeerPtrs
     }
 }
 
+// The unit of one algorithm's four MX families: fmi_fused_mx_*.hip, _mx_sr_, _mxfp4_, _mxfp4_sr_.
+template <int ALG>
+MxUnit* mx_family(bool fp4, bool sr) {
+    if (fp4) return sr ? &mxfp4_unit<ALG, true> : &mxfp4_unit<ALG, false>;
+    return sr ? &mx_unit<ALG, true> : &mx_unit<ALG, false>;
+}
+
 int launch_fused_mx(int alg, int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s) {
-    if (mx.seed) {  // stochastic rounding: fmi_fused_mxfp4_sr_*.hip, fmi_fused_mx_sr_*.hip; the element type's own output
-        if (out_dtype != dtype) return fail(FMI_ERR_INVALID, "fused MX stochastic-rounding launch: the output is the element type's");
-        const bool fp4 = dtype == FMI_F4E2M1;
-        switch (alg) {
-            case sched::kAllreduce:
-                return fp4 ? mxfp4_sr_unit<sched::kAllreduce>(P, ptrs, mx, n, s) : mx_sr_unit<sched::kAllreduce>(dtype, P, ptrs, mx, n, s);
-            case sched::kReduce: return fp4 ? mxfp4_sr_unit<sched::kReduce>(P, ptrs, mx, n, s) : mx_sr_unit<sched::kReduce>(dtype, P, ptrs, mx, n, s);
-            case sched::kReduceLtr:
-                return fp4 ? mxfp4_sr_unit<sched::kReduceLtr>(P, ptrs, mx, n, s) : mx_sr_unit<sched::kReduceLtr>(dtype, P, ptrs, mx, n, s);
-            default: return fail(FMI_ERR_INVALID, "fused MX stochastic-rounding launch: no kernel for algorithm " + std::to_string(alg));
-        }
-    }
-    if (dtype == FMI_F4E2M1) {  // MXFP4: fmi_fused_mxfp4_*.hip
-        switch (alg) {
-            case sched::kAllreduce: return mxfp4_unit<sched::kAllreduce>(out_dtype, P, ptrs, mx, n, s);
-            case sched::kReduce: return mxfp4_unit<sched::kReduce>(out_dtype, P, ptrs, mx, n, s);
-            case sched::kReduceLtr: return mxfp4_unit<sched::kReduceLtr>(out_dtype, P, ptrs, mx, n, s);
-            default: return fail(FMI_ERR_INVALID, "fused MXFP4 launch: no kernel for algorithm " + std::to_string(alg));
-        }
-    }
+    const bool fp4 = dtype == FMI_F4E2M1, sr = mx.seed != nullptr;
+    if (sr && out_dtype != dtype) return fail(FMI_ERR_INVALID, "fused MX stochastic-rounding launch: the output is the element type's");
     switch (alg) {
-        case sched::kAllreduce: return mx_unit<sched::kAllreduce>(dtype, out_dtype, P, ptrs, mx, n, s);
-        case sched::kReduce: return mx_unit<sched::kReduce>(dtype, out_dtype, P, ptrs, mx, n, s);
-        case sched::kReduceLtr: return mx_unit<sched::kReduceLtr>(dtype, out_dtype, P, ptrs, mx, n, s);
-        default: return fail(FMI_ERR_INVALID, "fused MX launch: no kernel for algorithm " + std::to_string(alg));
+        case sched::kAllreduce: return mx_family<sched::kAllreduce>(fp4, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
+        case sched::kReduce: return mx_family<sched::kReduce>(fp4, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
+        case sched::kReduceLtr: return mx_family<sched::kReduceLtr>(fp4, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
+        default:
+            return fail(FMI_ERR_INVALID, std::string("fused ") + (sr ? "MX stochastic-rounding" : fp4 ? "MXFP4" : "MX") +
+                                             " launch: no kernel for algorithm " + std::to_string(alg));
     }
 }
 

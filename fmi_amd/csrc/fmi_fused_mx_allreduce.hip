@@ -3,5 +3,5 @@
 #include "fmi_mx_impl.h"
 
 namespace fmi::dev {
-template MxUnit mx_unit<sched::kAllreduce>;
+template MxUnit mx_unit<sched::kAllreduce, false>;
 }  // namespace fmi::dev

@@ -3,5 +3,5 @@
 #include "fmi_mx_impl.h"
 
 namespace fmi::dev {
-template MxUnit mx_unit<sched::kReduce>;
+template MxUnit mx_unit<sched::kReduce, false>;
 }  // namespace fmi::dev

@@ -3,5 +3,5 @@
 #include "fmi_mx_impl.h"
 
 namespace fmi::dev {
-template MxUnit mx_unit<sched::kReduceLtr>;
+template MxUnit mx_unit<sched::kReduceLtr, false>;
 }  // namespace fmi::dev

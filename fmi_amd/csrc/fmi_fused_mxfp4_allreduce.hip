@@ -3,5 +3,5 @@
 #include "fmi_mxfp4_impl.h"
 
 namespace fmi::dev {
-template Mxfp4Unit mxfp4_unit<sched::kAllreduce>;
+template MxUnit mxfp4_unit<sched::kAllreduce, false>;
 }  // namespace fmi::dev

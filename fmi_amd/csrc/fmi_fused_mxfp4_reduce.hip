@@ -3,5 +3,5 @@
 #include "fmi_mxfp4_impl.h"
 
 namespace fmi::dev {
-template Mxfp4Unit mxfp4_unit<sched::kReduce>;
+template MxUnit mxfp4_unit<sched::kReduce, false>;
 }  // namespace fmi::dev

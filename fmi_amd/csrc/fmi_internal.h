@@ -268,30 +268,24 @@ struct MxArgs {
 // The fused MX kernels (fmi_fused.hip -> fmi_fused_mx_*.hip): 2 <= P <= 16, the element buckets 16-B aligned, the
 // scale arrays of any alignment. alg, dtype, out_dtype, ptrs as launch_fused_scaled's.
 int launch_fused_mx(int alg, int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
-// One translation unit's MX kernels (algorithm ALG, P = 2..16, both dtypes, both outputs): defined in fmi_mx_impl.h,
-// instantiated by one fmi_fused_mx_*.hip each.
+// One translation unit's MX kernels: algorithm ALG, P = 2..16, one of four families, the element format by the
+// template's name and the rounding by SR.
+//   mx_unit<ALG, false>      both 8-bit floats, 8-bit and f32 output    fmi_mx_impl.h, one fmi_fused_mx_*.hip each
+//   mx_unit<ALG, true>       both 8-bit floats, stochastic rounding     fmi_mx_impl.h, one fmi_fused_mx_sr_*.hip each
+//   mxfp4_unit<ALG, false>   FMI_F4E2M1, E2M1 and f32 output            fmi_mxfp4_impl.h, one fmi_fused_mxfp4_*.hip each
+//   mxfp4_unit<ALG, true>    FMI_F4E2M1, stochastic rounding            fmi_mxfp4_impl.h, one fmi_fused_mxfp4_sr_*.hip each
+// A stochastic-rounding unit (mx.seed != nullptr) holds the element type's own output only: out_dtype == dtype.
+// n counts elements (FMI_F4E2M1: two to a byte).
 using MxUnit = int(int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
-template <int ALG>
+template <int ALG, bool SR>
 MxUnit mx_unit;
-// The MXFP4 kernels of one algorithm (dtype FMI_F4E2M1, P = 2..16, both outputs; n counts elements, two to a byte):
-// defined in fmi_mxfp4_impl.h, instantiated by one fmi_fused_mxfp4_*.hip each. launch_fused_mx sends dtype FMI_F4E2M1 here.
-using Mxfp4Unit = int(int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
-template <int ALG>
-Mxfp4Unit mxfp4_unit;
-// The stochastic-rounding kernels of the same two families (mx.seed != nullptr; the element type's own output only):
-// defined in fmi_mx_sr_impl.h / fmi_mxfp4_sr_impl.h, instantiated by one fmi_fused_mx_sr_*.hip /
-// fmi_fused_mxfp4_sr_*.hip each. launch_fused_mx sends a call with a seed here.
-using MxSrUnit = int(int dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
-template <int ALG>
-MxSrUnit mx_sr_unit;
-using Mxfp4SrUnit = int(int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
-template <int ALG>
-Mxfp4SrUnit mxfp4_sr_unit;
+template <int ALG, bool SR>
+MxUnit mxfp4_unit;
 // fmi_dev_mx_dequantize / fmi_dev_mx_quantize (fmi_mx.hip), any alignment, one launch each. dtype: FMI_F8E4M3,
 // FMI_F8E5M2 or FMI_F4E2M1 (packed: n elements in ceil(n / 2) bytes); dst_dtype / src_dtype: FMI_F32, FMI_F16 or FMI_BF16 (FMI_ERR_INVALID otherwise).
 int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s);
 int launch_mx_quantize(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s);
-// fmi_dev_mx_quantize_sr: launch_mx_quantize with narrow_sr (fmi_mx_sr.h); seed one u64 in device memory, first the
+// fmi_dev_mx_quantize_sr (fmi_mx.hip too): launch_mx_quantize with narrow_sr (fmi_mx_sr.h); seed one u64 in device memory, first the
 // stream position of element 0 (a multiple of 32).
 int launch_mx_quantize_sr(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, const uint64_t* seed,
                           uint64_t first, hipStream_t s);

@@ -9,6 +9,8 @@
 // FMI_F4E2M1 (two elements to a byte): one BYTE per thread and step, so nothing needs sub-byte addressing or atomics;
 // a block of 32 elements is 16 threads, a quarter of a wave, and its amax four shuffles inside the quarter. Table
 // widening and the integer-code narrowing of fmi_mxfp4_impl.h.
+// fmi_dev_mx_quantize_sr, which is also what a fmi_dev_reduce_tree_mx_sr call beyond the fused kernels ends with, is the
+// quantize kernels' SR instantiation: out = narrow_sr(fl32(S * 2^(127 - e_out)), r) (fmi_mx_sr.h).
 #include "fmi_mxfp4_impl.h"
 
 namespace fmi::dev {
@@ -28,8 +30,22 @@ __global__ void __launch_bounds__(kBlock) mx_dequantize_kernel(D* dst, const T* 
     }
 }
 
-template <class T, class S>
-__global__ void __launch_bounds__(kBlock) mx_quantize_kernel(T* out, uint8_t* out_scales, const S* src, size_t n) {
+// What a stochastic-rounding quantize kernel takes beside the round-to-nearest one's arguments: the device word that
+// holds the Philox key and the stream position of element 0. The kernels take it as a parameter pack SR..., empty for
+// round to nearest (an unused argument, even an empty struct, would move that kernel's hidden arguments).
+struct SrStream {
+    const uint64_t* seed;
+    uint64_t first;
+};
+
+// SR: narrow_sr (fmi_mx_sr.h) where the round-to-nearest kernel narrows. A thread runs the Philox call of its element's
+// group of 8 and keeps 16 bits of it.
+template <class T, class S, class... SR>
+__global__ void __launch_bounds__(kBlock) mx_quantize_kernel(T* out, uint8_t* out_scales, const S* src, size_t n, SR... sr) {
+    constexpr bool kSr = sizeof...(SR) != 0;
+    const SrStream stream{sr...};
+    uint64_t seed = 0;
+    if constexpr (kSr) seed = *stream.seed;
     const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
     const unsigned lane = threadIdx.x % 64;
     // `wave0`: the first element of this wave's 64 (two blocks); the loop's condition is the wave's, not the lane's
@@ -48,7 +64,13 @@ __global__ void __launch_bounds__(kBlock) mx_quantize_kernel(T* out, uint8_t* ou
         const uint32_t e_out = mx_scale_byte<T>(A);
         const float y = x * mx_inv_scale(e_out);
         if (have) {
-            out[i] = e_out == 255u ? T{0x7F} : fp8_narrow<T>(y);
+            if constexpr (kSr) {
+                const uint64_t j = stream.first + i;
+                const uint32_t code = fp8_narrow_sr<T>(y, sr_bits(philox4x32_10(j >> 3, seed), j));
+                out[i] = T{static_cast<uint8_t>(e_out == 255u ? 0x7Fu : code)};
+            } else {
+                out[i] = e_out == 255u ? T{0x7F} : fp8_narrow<T>(y);
+            }
             if (lane % 32 == 0) out_scales[i / 32] = static_cast<uint8_t>(e_out);
         }
     }
@@ -72,8 +94,13 @@ __global__ void __launch_bounds__(kBlock) mxfp4_dequantize_kernel(D* dst, const 
     }
 }
 
-template <class S>
-__global__ void __launch_bounds__(kBlock) mxfp4_quantize_kernel(uint8_t* out, uint8_t* out_scales, const S* src, size_t n) {
+// SR: as mx_quantize_kernel's; a byte's elements 2 i and 2 i + 1 lie in one Philox group because `first` is even.
+template <class S, class... SR>
+__global__ void __launch_bounds__(kBlock) mxfp4_quantize_kernel(uint8_t* out, uint8_t* out_scales, const S* src, size_t n, SR... sr) {
+    constexpr bool kSr = sizeof...(SR) != 0;
+    const SrStream stream{sr...};
+    uint64_t seed = 0;
+    if constexpr (kSr) seed = *stream.seed;
     const size_t nbytes = n / 2 + n % 2;
     const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
     const unsigned lane = threadIdx.x % 64;
@@ -94,7 +121,15 @@ __global__ void __launch_bounds__(kBlock) mxfp4_quantize_kernel(uint8_t* out, ui
         const uint32_t e_out = mxfp4_scale_byte(A);
         const float inv = mx_inv_scale(e_out);
         if (i < nbytes) {
-            const uint32_t b = e_out == 255u ? 0u : fp4_narrow_sw(x[0] * inv) | (fp4_narrow_sw(x[1] * inv) << 4);
+            uint32_t b;
+            if constexpr (kSr) {
+                const uint64_t j = stream.first + 2 * i;  // even: j and j + 1 share the word (j & 7) >> 1 of one Philox group
+                const uint32_t w = philox4x32_10(j >> 3, seed).w[(static_cast<uint32_t>(j) & 7u) >> 1];
+                const uint32_t hi = 2 * i + 1 < n ? fp4_narrow_sr(x[1] * inv, w >> 16) : 0u;  // an odd bucket's last high nibble: 0
+                b = e_out == 255u ? 0u : fp4_narrow_sr(x[0] * inv, w & 0xFFFFu) | (hi << 4);
+            } else {
+                b = e_out == 255u ? 0u : fp4_narrow_sw(x[0] * inv) | (fp4_narrow_sw(x[1] * inv) << 4);
+            }
             out[i] = static_cast<uint8_t>(b);
             if (lane % 16 == 0) out_scales[i / 16] = static_cast<uint8_t>(e_out);
         }
@@ -115,6 +150,25 @@ int with_wide_dtype(const char* who, const char* what, int dtype, F&& f) {
     }
 }
 
+// fmi_dev_mx_quantize (no sr) and fmi_dev_mx_quantize_sr (one SrStream), `who` in their messages.
+template <class... SR>
+int quantize(const char* who, int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s, SR... sr) {
+    constexpr bool kSr = sizeof...(SR) != 0;
+    if (n == 0) return FMI_OK;
+    if (dtype == FMI_F4E2M1)
+        return with_wide_dtype(who, "src_dtype", src_dtype, [&]<class S>() -> int {
+            mxfp4_quantize_kernel<<<grid_of(n / 2 + n % 2), kBlock, 0, s>>>(static_cast<uint8_t*>(out), out_scales, static_cast<const S*>(src), n,
+                                                                           sr...);
+            return check_launch(kSr ? "MXFP4 stochastic-rounding quantize kernel launch" : "MXFP4 quantize kernel launch");
+        });
+    return with_dtype<kTierFp8>(dtype, [&]<class T>() -> int {
+        return with_wide_dtype(who, "src_dtype", src_dtype, [&]<class S>() -> int {
+            mx_quantize_kernel<<<grid_of(n), kBlock, 0, s>>>(static_cast<T*>(out), out_scales, static_cast<const S*>(src), n, sr...);
+            return check_launch(kSr ? "MX stochastic-rounding quantize kernel launch" : "MX quantize kernel launch");
+        });
+    });
+}
+
 }  // namespace
 
 int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s) {
@@ -133,18 +187,12 @@ int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, c
 }
 
 int launch_mx_quantize(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s) {
-    if (n == 0) return FMI_OK;
-    if (dtype == FMI_F4E2M1)
-        return with_wide_dtype("fmi_dev_mx_quantize", "src_dtype", src_dtype, [&]<class S>() -> int {
-            mxfp4_quantize_kernel<S><<<grid_of(n / 2 + n % 2), kBlock, 0, s>>>(static_cast<uint8_t*>(out), out_scales, static_cast<const S*>(src), n);
-            return check_launch("MXFP4 quantize kernel launch");
-        });
-    return with_dtype<kTierFp8>(dtype, [&]<class T>() -> int {
-        return with_wide_dtype("fmi_dev_mx_quantize", "src_dtype", src_dtype, [&]<class S>() -> int {
-            mx_quantize_kernel<T, S><<<grid_of(n), kBlock, 0, s>>>(static_cast<T*>(out), out_scales, static_cast<const S*>(src), n);
-            return check_launch("MX quantize kernel launch");
-        });
-    });
+    return quantize("fmi_dev_mx_quantize", dtype, out, out_scales, src_dtype, src, n, s);
+}
+
+int launch_mx_quantize_sr(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, const uint64_t* seed,
+                          uint64_t first, hipStream_t s) {
+    return quantize("fmi_dev_mx_quantize_sr", dtype, out, out_scales, src_dtype, src, n, s, SrStream{seed, first});
 }
 
 }  // namespace fmi::dev

@@ -1,6 +1,6 @@
 // fmi_mx_sr.h — stochastic rounding for the MX calls (fmi_dev_reduce_tree_mx_sr, fmi_dev_mx_quantize_sr,
 // fmi_host_mx_quantize_sr; include/fmi_dev.h): the random bits and the rounding, one __host__ __device__ function each,
-// shared by the fused kernels (fmi_mx_sr_impl.h, fmi_mxfp4_sr_impl.h), the quantize kernels and the host call
+// shared by the fused kernels (fmi_mx_impl.h, fmi_mxfp4_impl.h), the quantize kernels (fmi_mx.hip) and the host call
 // (fmi_mx_sr.hip). Plain C++: no conversion instruction of the target is used.
 //
 //   element i of a call has the stream position j = first + i; q = j >> 3

@@ -1,98 +1,11 @@
-// The stochastic-rounding MX calls beside the fused kernels (include/fmi_dev.h): fmi_dev_mx_quantize_sr's kernels, which
-// are also what a fmi_dev_reduce_tree_mx_sr call beyond the fused kernels (P = 1, P > 16, unaligned buckets) ends with,
-// and fmi_host_mx_quantize_sr, the same quantization on host memory.
+// fmi_host_mx_quantize_sr (include/fmi_dev.h): fmi_dev_mx_quantize_sr's quantization on host memory, from the functions
+// the kernels use (fmi_mx_sr.h, and the scale-byte rules of fmi_mx_impl.h / fmi_mxfp4_impl.h). Host code only: the
+// kernels of the device call are the quantize kernels' SR instantiations (fmi_mx.hip).
 //   per block of 32: A = umax bits(|S|), e_out = the block's scale byte, out = narrow_sr(fl32(S * 2^(127 - e_out)), r)
-// The kernels are mx_quantize_kernel and mxfp4_quantize_kernel (fmi_mx.hip) with narrow_sr (fmi_mx_sr.h): one element
-// (E2M1: one byte, two elements) per thread and step, the amax by shuffles inside a half (quarter) of a wave. A thread
-// runs the Philox call of its element's group of 8 and keeps 16 (32) bits of it: these are the fallback's passes, not a
-// hot path. An E2M1 byte's elements 2 i and 2 i + 1 lie in one group because `first` is even.
 #include "fmi_mxfp4_impl.h"
-#include "fmi_mx_sr.h"
 
 namespace fmi::dev {
 namespace {
-
-constexpr unsigned kBlock = 256;  // a multiple of 64: waves start on block boundaries
-constexpr size_t kGridCap = size_t(1) << 20;
-
-template <class T, class S>
-__global__ void __launch_bounds__(kBlock) mx_quantize_sr_kernel(T* out, uint8_t* out_scales, const S* src, size_t n, const uint64_t* seed_ptr,
-                                                                uint64_t first) {
-    const uint64_t seed = *seed_ptr;
-    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-    const unsigned lane = threadIdx.x % 64;
-    // `wave0`: the first element of this wave's 64 (two blocks); the loop's condition is the wave's, not the lane's
-    for (size_t wave0 = static_cast<size_t>(blockIdx.x) * blockDim.x + (threadIdx.x - lane); wave0 < n; wave0 += stride) {
-        const size_t i = wave0 + lane;
-        const bool have = i < n;
-        float x = 0.0f;
-        if (have) {
-            Lanes<S, 1> raw;
-            raw.v[0] = src[i];
-            x = to_value<float>(raw).v[0];
-        }
-        uint32_t A = mx_abs_bits(x);  // 0 beyond the bucket
-#pragma unroll
-        for (int d = 16; d > 0; d >>= 1) A = max(A, static_cast<uint32_t>(__shfl_xor(static_cast<int>(A), d, 64)));
-        const uint32_t e_out = mx_scale_byte<T>(A);
-        const float y = x * mx_inv_scale(e_out);
-        if (have) {
-            const uint64_t j = first + i;
-            const uint32_t code = fp8_narrow_sr<T>(y, sr_bits(philox4x32_10(j >> 3, seed), j));
-            out[i] = T{static_cast<uint8_t>(e_out == 255u ? 0x7Fu : code)};
-            if (lane % 32 == 0) out_scales[i / 32] = static_cast<uint8_t>(e_out);
-        }
-    }
-}
-
-// n: elements; the bucket is n / 2 + n % 2 bytes, and the last byte's high nibble is not an element when n is odd.
-template <class S>
-__global__ void __launch_bounds__(kBlock) mxfp4_quantize_sr_kernel(uint8_t* out, uint8_t* out_scales, const S* src, size_t n,
-                                                                   const uint64_t* seed_ptr, uint64_t first) {
-    const uint64_t seed = *seed_ptr;
-    const size_t nbytes = n / 2 + n % 2;
-    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-    const unsigned lane = threadIdx.x % 64;
-    // `wave0`: the first byte of this wave's 64 (four blocks); the loop's condition is the wave's, not the lane's
-    for (size_t wave0 = static_cast<size_t>(blockIdx.x) * blockDim.x + (threadIdx.x - lane); wave0 < nbytes; wave0 += stride) {
-        const size_t i = wave0 + lane;
-        float x[2] = {0.0f, 0.0f};  // beyond the bucket: +0; an odd bucket's last high nibble is written 0 below
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-            if (2 * i + k < n) {
-                Lanes<S, 1> raw;
-                raw.v[0] = src[2 * i + k];
-                x[k] = to_value<float>(raw).v[0];
-            }
-        uint32_t A = max(mx_abs_bits(x[0]), mx_abs_bits(x[1]));
-#pragma unroll
-        for (int d = 8; d > 0; d >>= 1) A = max(A, static_cast<uint32_t>(__shfl_xor(static_cast<int>(A), d, 64)));
-        const uint32_t e_out = mxfp4_scale_byte(A);
-        const float inv = mx_inv_scale(e_out);
-        if (i < nbytes) {
-            const uint64_t j = first + 2 * i;  // even: j and j + 1 share the word (j & 7) >> 1 of one Philox group
-            const uint32_t w = philox4x32_10(j >> 3, seed).w[(static_cast<uint32_t>(j) & 7u) >> 1];
-            const uint32_t hi = 2 * i + 1 < n ? fp4_narrow_sr(x[1] * inv, w >> 16) : 0u;
-            const uint32_t b = e_out == 255u ? 0u : fp4_narrow_sr(x[0] * inv, w & 0xFFFFu) | (hi << 4);
-            out[i] = static_cast<uint8_t>(b);
-            if (lane % 16 == 0) out_scales[i / 16] = static_cast<uint8_t>(e_out);
-        }
-    }
-}
-
-unsigned grid_of(size_t n) { return static_cast<unsigned>(std::min(grid_for(n, kBlock), kGridCap)); }
-
-// f.template operator()<S>() for the source of a quantization: FMI_F32, FMI_F16 or FMI_BF16.
-template <class F>
-int with_src_dtype(int dtype, F&& f) {
-    switch (dtype) {
-        case FMI_F32: return f.template operator()<float>();
-        case FMI_F16: return f.template operator()<_Float16>();
-        case FMI_BF16: return f.template operator()<__bf16>();
-        default:
-            return fail(FMI_ERR_INVALID, "fmi_dev_mx_quantize_sr: src_dtype " + std::to_string(dtype) + " must be FMI_F32, FMI_F16 or FMI_BF16");
-    }
-}
 
 // One block of 32 (or fewer) host elements; i0: the block's first element in the call. scale_byte: the kernels' own
 // mx_scale_byte<T> or mxfp4_scale_byte.
@@ -114,23 +27,6 @@ void host_block(const float* src, size_t i0, size_t len, uint8_t* scale, uint64_
 }
 
 }  // namespace
-
-int launch_mx_quantize_sr(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, const uint64_t* seed,
-                          uint64_t first, hipStream_t s) {
-    if (n == 0) return FMI_OK;
-    if (dtype == FMI_F4E2M1)
-        return with_src_dtype(src_dtype, [&]<class S>() -> int {
-            mxfp4_quantize_sr_kernel<S><<<grid_of(n / 2 + n % 2), kBlock, 0, s>>>(static_cast<uint8_t*>(out), out_scales, static_cast<const S*>(src),
-                                                                                 n, seed, first);
-            return check_launch("MXFP4 stochastic-rounding quantize kernel launch");
-        });
-    return with_dtype<kTierFp8>(dtype, [&]<class T>() -> int {
-        return with_src_dtype(src_dtype, [&]<class S>() -> int {
-            mx_quantize_sr_kernel<T, S><<<grid_of(n), kBlock, 0, s>>>(static_cast<T*>(out), out_scales, static_cast<const S*>(src), n, seed, first);
-            return check_launch("MX stochastic-rounding quantize kernel launch");
-        });
-    });
-}
 
 // fmi_host_mx_quantize_sr after its checks. A NaN block (~0u from host_block): 0x7F bytes, zero nibbles.
 int host_mx_quantize_sr(int dtype, void* out, uint8_t* out_scales, const float* src, size_t n, uint64_t seed, uint64_t first) {

@@ -1,6 +1,6 @@
 // fmi_mxfp4_impl.h — the MXFP4 kernels of fmi_dev_reduce_tree_mx (include/fmi_dev.h): the sum or mean of block-scaled
-// E2M1 buckets, two elements to a byte, one E8M0 scale byte per 32 elements. Included by the fmi_fused_mxfp4_*.hip
-// translation units and fmi_mx.hip alone.
+// E2M1 buckets, two elements to a byte, one E8M0 scale byte per 32 elements, and of fmi_dev_reduce_tree_mx_sr at that
+// type. Included by the fmi_fused_mxfp4_*.hip translation units, fmi_mx.hip and fmi_mx_sr.hip alone.
 //
 //   v_p = fl32(widen(x_p) * scale32(e_p[b]));  S = F32_program(v);  S = fl32(S * r)      (r = fl32(1 / P) or 1)
 //   f32 output:   out = S
@@ -22,6 +22,14 @@
 // at the scale operand 1.0f: the E8M0 scale and the inverse scale are applied by separate IEEE f32 multiplies
 // (v_pk_mul_f32), so what the instructions do with a NaN scale or the subnormal-encoded 2^-127 never matters. The
 // ragged block, the fallback's kernels (fmi_mx.hip) and the host use the integer-code forms below.
+//
+// Stochastic rounding (fmi_dev_reduce_tree_mx_sr at FMI_F4E2M1; the template flag SR, E2M1 output only) is the same
+// kernel with narrow_sr (fmi_mx_sr.h) where the round-to-nearest one narrows. One lane is one block b of 32 elements at
+// the stream positions first + 32 b + k: four whole Philox groups, q = (first >> 3) + 4 b + K for piece K, whose output
+// word k holds r of the piece's elements 2 k and 2 k + 1, the two lanes of Fp8Half::p[k] and the two nibbles of byte k of
+// output word K. A group's four words are dead once its piece is narrowed, so one Philox state is live at a time beside
+// the 32 results. That narrowing is a few exact f32 operations per element, not the packed conversion instruction: that
+// one rounds to nearest, and its stochastic form was not shown to follow this definition.
 #pragma once
 
 #include "fmi_mx_impl.h"
@@ -90,9 +98,18 @@ __device__ __forceinline__ Fp8Half mxfp4_piece(const Fp8Words* raw, const float*
     return S;
 }
 
-// POL, group0, lane: as mx_group. b = group0 + lane is the lane's BLOCK: bytes 16 b .. 16 b + 15 of every bucket.
-template <int ALG, int P, bool OUT32, bool POL>
-__device__ __forceinline__ void mxfp4_block(const PeerPtrs& ptrs, const MxArgs& mx, size_t group0, unsigned lane) {
+// The 8 nibbles of one piece under narrow_sr, from the Philox output of its 8 elements.
+__device__ __forceinline__ uint32_t fp4_narrow_sr_word(const Fp8Half& v, const Philox4& W) {
+    uint32_t w = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        w |= (fp4_narrow_sr(v.p[k].x, W.w[k] & 0xFFFFu) | (fp4_narrow_sr(v.p[k].y, W.w[k] >> 16) << 4)) << (8 * k);
+    return w;
+}
+
+// POL, group0, lane, seed, q0: as mx_group. b = group0 + lane is the lane's BLOCK: bytes 16 b .. 16 b + 15 of every bucket.
+template <int ALG, int P, bool OUT32, bool SR, bool POL>
+__device__ __forceinline__ void mxfp4_block(const PeerPtrs& ptrs, const MxArgs& mx, uint64_t seed, uint64_t q0, size_t group0, unsigned lane) {
     const size_t b = group0 + lane;
     const Fp8Access<POL, kTreeStoreAux, uint8_t> acc{POL ? group0 * 16 : b * 16, POL ? lane * 16u : 0u};
     Fp8Words raw[P];
@@ -130,7 +147,13 @@ __device__ __forceinline__ void mxfp4_block(const PeerPtrs& ptrs, const MxArgs& 
         for (int K = 0; K < 4; ++K) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) S[K].p[k] = S[K].p[k] * inv;
-            out.w[K] = e_out == 255u ? 0u : fp4_narrow_word(S[K]);  // a NaN block: scale byte 255, every nibble 0
+            // a NaN block: scale byte 255, every nibble 0
+            if constexpr (SR) {
+                const uint32_t w = fp4_narrow_sr_word(S[K], philox4x32_10(q0 + 4 * b + K, seed));
+                out.w[K] = e_out == 255u ? 0u : w;
+            } else {
+                out.w[K] = e_out == 255u ? 0u : fp4_narrow_word(S[K]);
+            }
         }
         acc.store(ptrs.out[0], out);
         mx.out_scales[b] = static_cast<uint8_t>(e_out);
@@ -138,17 +161,20 @@ __device__ __forceinline__ void mxfp4_block(const PeerPtrs& ptrs, const MxArgs& 
 }
 
 // The grid of fp8_mx_kernel over the n / 32 whole blocks; the first wave of workgroup 0 takes the ragged last block.
-template <int ALG, int P, bool OUT32>
+template <int ALG, int P, bool OUT32, bool SR>
 __global__ void __launch_bounds__(256) mxfp4_kernel(PeerPtrs ptrs, MxArgs mx, size_t n, int pol) {
+    static_assert(!(SR && OUT32), "stochastic rounding exists only with the element type's own output");
+    uint64_t seed = 0, q0 = 0;  // a round-to-nearest kernel reads neither
+    if constexpr (SR) seed = *mx.seed, q0 = mx.first >> 3;
     const size_t nblk = n / 32;
     if (pol == 1) {
         const size_t B = blockDim.x;
         for (size_t tile = blockIdx.x; tile * B < nblk; tile += gridDim.x)
-            if (tile * B + threadIdx.x < nblk) mxfp4_block<ALG, P, OUT32, true>(ptrs, mx, tile * B, threadIdx.x);
+            if (tile * B + threadIdx.x < nblk) mxfp4_block<ALG, P, OUT32, SR, true>(ptrs, mx, seed, q0, tile * B, threadIdx.x);
     } else {
         const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
         for (size_t b = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; b < nblk; b += stride)
-            mxfp4_block<ALG, P, OUT32, false>(ptrs, mx, b, 0u);
+            mxfp4_block<ALG, P, OUT32, SR, false>(ptrs, mx, seed, q0, b, 0u);
     }
     const size_t first = nblk * 32;
     if (blockIdx.x == 0 && threadIdx.x < 64 && first < n) {  // one whole wave: uniform for the exchanges below
@@ -174,7 +200,14 @@ __global__ void __launch_bounds__(256) mxfp4_kernel(PeerPtrs ptrs, MxArgs mx, si
             for (int d = 32; d > 0; d >>= 1) A = max(A, static_cast<uint32_t>(__shfl_xor(static_cast<int>(A), d, 64)));
             const uint32_t e_out = mxfp4_scale_byte(A);
             // beyond the block: code 0, which is what an odd bucket's last high nibble takes
-            const uint32_t code = have && e_out != 255u ? fp4_narrow_sw(S * mx_inv_scale(e_out)) : 0u;
+            uint32_t code;
+            if constexpr (SR) {
+                const uint64_t j = mx.first + i;
+                const uint32_t sr = fp4_narrow_sr(S * mx_inv_scale(e_out), sr_bits(philox4x32_10(j >> 3, seed), j));
+                code = have && e_out != 255u ? sr : 0u;
+            } else {
+                code = have && e_out != 255u ? fp4_narrow_sw(S * mx_inv_scale(e_out)) : 0u;
+            }
             const uint32_t next = static_cast<uint32_t>(__shfl_xor(static_cast<int>(code), 1, 64));
             if (have && shift == 0u) static_cast<uint8_t*>(ptrs.out[0])[i / 2] = static_cast<uint8_t>(code | (next << 4));
             if (threadIdx.x == 0) mx.out_scales[nblk] = static_cast<uint8_t>(e_out);
@@ -182,28 +215,34 @@ __global__ void __launch_bounds__(256) mxfp4_kernel(PeerPtrs ptrs, MxArgs mx, si
     }
 }
 
-template <int ALG, bool OUT32, int P>
+template <int ALG, bool OUT32, bool SR, int P>
 void mxfp4_one(const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s) {
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(grid_for(n / 32, kFusedBlock), kFusedGridCap));
     // mx_one's in-flight budget (fmi_mx_impl.h): a workgroup loads the same 4 KiB per peer
     const size_t lds = fused_lds_bytes(P, kFusedBlock * 8);
-    mxfp4_kernel<ALG, P, OUT32><<<grid, kFusedBlock, lds, s>>>(ptrs, mx, n, fused_policy(false, P));
+    mxfp4_kernel<ALG, P, OUT32, SR><<<grid, kFusedBlock, lds, s>>>(ptrs, mx, n, fused_policy(false, P));
 }
 
-template <int ALG, bool OUT32, int... I>
+template <int ALG, bool OUT32, bool SR, int... I>
 constexpr std::array<MxFn, sizeof...(I)> mxfp4_table(std::integer_sequence<int, I...>) {
-    return {&mxfp4_one<ALG, OUT32, I + 2>...};
+    return {&mxfp4_one<ALG, OUT32, SR, I + 2>...};
 }
 
-template <int ALG>
-int mxfp4_unit(int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s) {
+// mx_unit's signature and its rule for SR; dtype is FMI_F4E2M1 (launch_fused_mx sends nothing else here).
+template <int ALG, bool SR>
+int mxfp4_unit(int, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s) {
     if (P < 2 || P > sched::kMaxFusedPeers)
-        return fail(FMI_ERR_INVALID, "fused MXFP4 kernel needs 2 <= P <= " + std::to_string(sched::kMaxFusedPeers) + ", got " + std::to_string(P));
+        return fail(FMI_ERR_INVALID, std::string(SR ? "fused MXFP4 stochastic-rounding" : "fused MXFP4") + " kernel needs 2 <= P <= " +
+                                         std::to_string(sched::kMaxFusedPeers) + ", got " + std::to_string(P));
     constexpr auto seq = std::make_integer_sequence<int, sched::kMaxFusedPeers - 1>{};
-    static constexpr auto same = mxfp4_table<ALG, false>(seq);
-    static constexpr auto wide = mxfp4_table<ALG, true>(seq);
-    (out_dtype == FMI_F32 ? wide : same)[P - 2](ptrs, mx, n, s);
-    return check_launch("fused MXFP4 P-way kernel launch");
+    static constexpr auto same = mxfp4_table<ALG, false, SR>(seq);
+    if constexpr (SR) {
+        same[P - 2](ptrs, mx, n, s);
+    } else {
+        static constexpr auto wide = mxfp4_table<ALG, true, false>(seq);
+        (out_dtype == FMI_F32 ? wide : same)[P - 2](ptrs, mx, n, s);
+    }
+    return check_launch(SR ? "fused MXFP4 stochastic-rounding P-way kernel launch" : "fused MXFP4 P-way kernel launch");
 }
 
 }  // namespace fmi::dev

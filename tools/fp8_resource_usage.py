@@ -15,7 +15,10 @@ Lines: fp8_acc_kernel<op, dtype, alg, P, scan>: vgpr .. agpr .. scratch .. occup
 (alg: 0 allreduce, 1 reduce, 2 reduce_ltr, 3 scan, 4 scan_ltr, 8 reduce partials);
 fp8_mx_kernel<dtype, alg, P, out32>, mx_quantize_kernel<dtype, source>, mx_dequantize_kernel<dtype, destination>;
 mxfp4_kernel<alg, P, out32>, mxfp4_quantize_kernel<source>, mxfp4_dequantize_kernel<destination> (the MXFP4 units,
-fmi_fused_mxfp4_*.hip, are part of --mx).
+fmi_fused_mxfp4_*.hip, are part of --mx). These are the round-to-nearest instantiations: fp8_mx_kernel and mxfp4_kernel
+have the rounding as one more, last, template argument, the quantize kernels the stochastic-rounding arguments as a
+trailing parameter pack, and a line shows neither. The stochastic-rounding instantiations of the same kernels
+(fmi_fused_mx_sr_*.hip, fmi_fused_mxfp4_sr_*.hip, and in fmi_mx.hip) are compiled with the rest and not listed.
 """
 import argparse
 import concurrent.futures
@@ -41,16 +44,17 @@ def describe(mangled):
         types = re.findall(r"NS\d*_(6f8e4m3|6f8e5m2)E|S\d*_|(DF16_|DF16b|f)", m.group(1))
         names = [FP8.get(a) or OTHER.get(b) or "same" for a, b in types]
         return "convert_kernel", 0, ", ".join(names + ["nt" if m.group(2) == "1" else "plain"])
-    m = re.search(r"13fp8_mx_kernelINS\d*_(6f8e4m3|6f8e5m2)ELi(\d+)ELi(\d+)ELb([01])EEE", mangled)
+    # the MX kernels' last template argument is the rounding: Lb0E, round to nearest, is listed (without it); Lb1E is not
+    m = re.search(r"13fp8_mx_kernelINS\d*_(6f8e4m3|6f8e5m2)ELi(\d+)ELi(\d+)ELb([01])ELb0EEE", mangled)
     if m:
         return "fp8_mx_kernel", int(m.group(3)), f"{FP8[m.group(1)]}, {m.group(2)}, {m.group(3)}, {'true' if m.group(4) == '1' else 'false'}"
-    m = re.search(r"\d+(mx_quantize_kernel|mx_dequantize_kernel)INS\d*_(6f8e4m3|6f8e5m2)E(DF16_|DF16b|f)EE", mangled)
+    m = re.search(r"\d+(mx_quantize_kernel|mx_dequantize_kernel)INS\d*_(6f8e4m3|6f8e5m2)E(DF16_|DF16b|f)(?:JE)?EE", mangled)
     if m:
         return m.group(1), 0, f"{FP8[m.group(2)]}, {OTHER[m.group(3)]}"
-    m = re.search(r"12mxfp4_kernelILi(\d+)ELi(\d+)ELb([01])EEE", mangled)
+    m = re.search(r"12mxfp4_kernelILi(\d+)ELi(\d+)ELb([01])ELb0EEE", mangled)
     if m:
         return "mxfp4_kernel", int(m.group(2)), f"{m.group(1)}, {m.group(2)}, {'true' if m.group(3) == '1' else 'false'}"
-    m = re.search(r"\d+(mxfp4_quantize_kernel|mxfp4_dequantize_kernel)I(DF16_|DF16b|f)EE", mangled)
+    m = re.search(r"\d+(mxfp4_quantize_kernel|mxfp4_dequantize_kernel)I(DF16_|DF16b|f)(?:JE)?EE", mangled)
     if m:
         return m.group(1), 0, OTHER[m.group(2)]
     return None
