@@ -1300,11 +1300,36 @@ struct KernelTiming {
     }
 };
 
+// The communicator's scratch slots (Comm::scratch): device buffers that grow to the largest size asked of them.
+enum Slot : int {
+    // a sharded collective's four: the zero-padded copy of `send` (shards_in), the N shards the all-to-all lands (the
+    // skewed allreduce carves its reduced shard behind them), the shard kernel's output (N versions of the shard for
+    // per-rank max / min, the sendbuf reduce and the scan), the padded result on its way to `recv` (shards_out)
+    kPadIn = 0,
+    kStaging = 1,
+    kReduced = 2,
+    kPadOut = 3,
+    // the host pipeline's chunks, in and out x HostPipe::kDepth
+    kHostIn0 = 4,
+    kHostIn1 = 5,
+    kHostOut0 = 6,
+    kHostOut1 = 7,
+    kChunks = 8,  // the pipelined allreduce: the same four for each of its two chunks in flight (chunk_slot), 8-15
+    kHostIn2 = 16,
+    kHostOut2 = 17,
+    kScaledWords = 18,  // the scaled allreduce's words: N scales, N amax words, this rank's amax word
+    // the MX allreduce's scale bytes, the four again
+    kMxScalePadIn = 19,
+    kMxScaleStaging = 20,
+    kMxScaleReduced = 21,
+    kMxScalePadOut = 22,
+};
+// chunk j's (0 or 1) slot in the role `of` (kPadIn .. kPadOut)
+constexpr Slot chunk_slot(int j, Slot of) { return static_cast<Slot>(kChunks + 4 * j + of); }
+
 struct Comm {
-    // 0-3: collective scratch; 4-7 and 16-17: host-pipeline chunk slots (in / out x HostPipe::kDepth);
-    // 8-15: pipelined-allreduce slots (2 x 4); 18: the scaled allreduce's words (N scales, N amax words, this rank's);
-    // 19-22: the MX allreduce's scale bytes (padded source, staging, reduced shard, gathered)
-    static constexpr int kSlots = 23;
+    static constexpr int kSlots = kMxScalePadOut + 1;
+    static_assert(kSlots == 23 && chunk_slot(1, kPadOut) + 1 == kHostIn2, "the slot layout");
     std::unique_ptr<Transport> t;
     std::mutex mu;
     KernelTiming timing;
@@ -1410,7 +1435,7 @@ struct Comm {
     }
 
     // scratch slot k of at least `bytes` (grown after draining the stream that used it)
-    int scratch(int k, size_t bytes, hipStream_t s, char** out) {
+    int scratch(Slot k, size_t bytes, hipStream_t s, char** out) {
         if (cap[k] < bytes) {
             FMI_COMM_HIP(hipStreamSynchronize(s));
             if (buf[k]) FMI_COMM_HIP(hipFree(buf[k]));
@@ -1447,13 +1472,24 @@ int aborted_error() {
     return fail(FMI_ERR_COMM, "communicator was aborted (a timeout or a transport error); destroy it");
 }
 
+// What every entry point asks before it touches the communicator, in this order. `lock`: taken on the communicator
+// before its transport is asked whether it was aborted.
+int check_ready(fmi_comm_t comm, std::unique_lock<std::mutex>* lock = nullptr) {
+    if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
+    if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
+    Comm* c = static_cast<Comm*>(comm);
+    if (lock) *lock = std::unique_lock<std::mutex>(c->mu);
+    if (c->t->aborted()) return aborted_error();
+    return FMI_OK;
+}
+
 // *kd: the dtype argument in canonical form, what the shard step hands to fmi_dev_reduce_tree / fmi_dev_scan_peers /
 // reduce_partials (FMI_ACC_F32 validated, dropped for max / min); *dtype: its storage dtype, for everything else
 // (sizes, the wire, order_sensitive).
 // FMI_OP_AVG (the mean over the ranks, float dtypes) passes where the call produces a reduction result (`no_avg` NULL);
 // `who` with `no_avg` set refuses it with that reason.
 int check_common(fmi_comm_t comm, int op, int* dtype, int* kd, const char* who = nullptr, const char* no_avg = nullptr) {
-    if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
+    if (!comm) return check_ready(comm);  // refused before the op and the dtype are looked at, the rest after them
     if (no_avg) FMI_COMM_RC(refuse_avg(op, who, no_avg));
     if (op != FMI_OP_AVG && (op < FMI_OP_SUM || op > FMI_OP_MIN)) return fail(FMI_ERR_INVALID, "unknown op " + std::to_string(op));
     FMI_COMM_RC(canonical_dtype(op, *dtype, true, 0, kd));
@@ -1462,25 +1498,86 @@ int check_common(fmi_comm_t comm, int op, int* dtype, int* kd, const char* who =
     if (dtype_size(*dtype) == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(*dtype));
     if (op == FMI_OP_AVG && !is_float(*dtype))
         return refuse_avg(op, "fmi_comm", ("dtype " + std::to_string(*dtype) + " is an integer dtype").c_str());
-    if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
-    if (static_cast<Comm*>(comm)->t->aborted()) return aborted_error();
-    return FMI_OK;
+    return check_ready(comm);
 }
 
 // NULL stream = the library's stream (fmi_stream_sync(NULL) then waits for the collective).
 hipStream_t resolve_stream(fmi_stream_t s) { return s ? static_cast<hipStream_t>(s) : library_stream(); }
 
-// Copy `send` (n elements) into a zero-padded staging bucket when the shard grid needs padding.
-int padded_source(Comm* c, size_t n, size_t padded, size_t esz, const void* send, hipStream_t s, const char** out) {
-    if (padded == n) {
-        *out = static_cast<const char*>(send);
-        return FMI_OK;
+// The reference's P = 1 collectives are copies: one rank skips the exchange unless the tunable sends it through.
+bool one_rank(const Transport& t) { return t.n() == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE); }
+int one_rank_copy(const void* send, void* recv, size_t bytes, hipStream_t s) {
+    return send != recv ? device_copy(recv, send, bytes, s) : FMI_OK;
+}
+
+// The shard grid of an n-element bucket over the ranks of a transport: rank k owns elements [k * shard, (k + 1) * shard)
+// of it, the last owners fewer (len) or none. One grid serves every byte stream cut along it (elements of any size, MX
+// scale bytes): a stream is given as its bytes per shard and its bytes in all.
+struct ShardGrid {
+    Transport& t;
+    const int N, rank;
+    const size_t n, shard, len;  // len: the true length of my shard
+    const bool exact;            // the shards cover the bucket with nothing over
+    ShardGrid(Transport& tr, size_t elems)
+        : t(tr), N(tr.n()), rank(tr.rank()), n(elems), shard(shard_elems(elems, N)), len(Transport::span(rank, shard, elems)),
+          exact(shard * N == elems) {}
+    // Do the shards move at their true lengths (no padded copies in or out)? Where the caller lets them and the
+    // transport can; the shard kernel then runs on len.
+    bool ragged(bool allowed) const { return allowed && !exact && t.ragged(); }
+};
+
+// The N inputs of a shard kernel: block j of `staging`.
+std::vector<const void*> shard_parts(const ShardGrid& g, const char* staging, size_t stride) {
+    std::vector<const void*> parts(g.N);
+    for (int j = 0; j < g.N; ++j) parts[j] = staging + j * stride;
+    return parts;
+}
+
+// `send` (total bytes) where its N shards of `bytes` each can be read whole: itself when they cover it, else a copy in
+// scratch slot `pad` with the rest zeroed. Judged on the stream's own bytes: the scale bytes or the FP4 bytes of a
+// bucket a few elements short of the grid can cover it where the elements do not.
+int padded_source(Comm* c, const ShardGrid& g, const void* send, size_t bytes, size_t total, Slot pad, hipStream_t s,
+                  const char** out) {
+    *out = static_cast<const char*>(send);
+    if (bytes * g.N == total) return FMI_OK;
+    char* p = nullptr;
+    FMI_COMM_RC(c->scratch(pad, bytes * g.N, s, &p));
+    FMI_COMM_RC(device_copy(p, send, total, s));
+    FMI_COMM_HIP(hipMemsetAsync(p + total, 0, bytes * g.N - total, s));
+    *out = p;
+    return FMI_OK;
+}
+
+// Shards in: staging[j * stride ...] = rank j's shard `rank` of `send`, a stream of `bytes` per shard and `total` in
+// all. ragged (ShardGrid::ragged): at the shards' true lengths; else straight from `send` when the shards cover the
+// stream, and through its zero-padded copy in slot `pad` when they do not.
+int shards_in(Comm* c, const ShardGrid& g, const void* send, size_t bytes, size_t total, bool ragged, Slot pad, char* staging,
+              size_t stride, hipStream_t s) {
+    if (ragged) return g.t.all_to_all_ragged(static_cast<const char*>(send), staging, bytes, total, s);
+    const char* src = nullptr;
+    FMI_COMM_RC(padded_source(c, g, send, bytes, total, pad, s, &src));
+    return g.t.all_to_all_strided(src, staging, bytes, stride, s);
+}
+
+// Shards out, the way back of the owners' results (`src`, `bytes` per shard) into the first `total` bytes of `dst`, on
+// transport t and stream s: every rank gets every owner's shard (kToAll), `root` alone does (kToRoot; dst is NULL on
+// the others), or rank j gets block j of every owner's N (kTransposed). ragged: at the shards' true lengths; else
+// straight into `dst` when the shards cover it, and through slot `pad` and a copy of `total` bytes when they do not.
+enum class Back { kToAll, kToRoot, kTransposed };
+int shards_out(Comm* c, const ShardGrid& g, Back to, int root, Transport& t, hipStream_t s, const char* src, void* dst,
+               size_t bytes, size_t total, bool ragged, Slot pad) {
+    char* out = static_cast<char*>(dst);
+    if (ragged) {
+        if (to == Back::kToAll) return t.all_gather_ragged(src, out, bytes, total, s);
+        if (to == Back::kToRoot) return t.gather_ragged(src, out, bytes, total, root, s);
+        return t.all_to_all_back_ragged(src, out, bytes, total, s);
     }
-    char* pad = nullptr;
-    FMI_COMM_RC(c->scratch(0, padded * esz, s, &pad));
-    FMI_COMM_RC(device_copy(pad, send, n * esz, s));
-    FMI_COMM_HIP(hipMemsetAsync(pad + n * esz, 0, (padded - n) * esz, s));
-    *out = pad;
+    const bool padded = bytes * g.N != total;
+    if (padded) FMI_COMM_RC(c->scratch(pad, bytes * g.N, s, &out));
+    if (to == Back::kToAll) FMI_COMM_RC(t.all_gather(src, out, bytes, s));
+    if (to == Back::kToRoot) FMI_COMM_RC(t.gather(src, out, bytes, root, s));
+    if (to == Back::kTransposed) FMI_COMM_RC(t.all_to_all(src, out, bytes, s));
+    if (padded && (to != Back::kToRoot || g.rank == root)) FMI_COMM_RC(device_copy(dst, out, total, s));
     return FMI_OK;
 }
 
@@ -1587,38 +1684,23 @@ int allreduce_tree_pipelined(Comm* c, int op, int dtype, int kd, int alg, const 
         const int j = static_cast<int>(k & 1);
         const size_t lo = k * ce;
         const size_t cn = std::min(ce, n - lo);
-        const size_t shard = shard_elems(cn, N);
-        const size_t padded = shard * N;
+        const ShardGrid g(*c->t, cn);  // only the last chunk can need padding
+        const size_t sb = g.shard * esz;
         const char* src = static_cast<const char*>(send) + lo * esz;
         char* dst = static_cast<char*>(recv) + lo * esz;
-        if (padded != cn) {  // only the last chunk can need padding
-            char* pad = nullptr;
-            FMI_COMM_RC(c->scratch(8 + 4 * j, padded * esz, s, &pad));
-            FMI_COMM_RC(device_copy(pad, src, cn * esz, s));
-            FMI_COMM_HIP(hipMemsetAsync(pad + cn * esz, 0, (padded - cn) * esz, s));
-            src = pad;
-        }
         char* staging = nullptr;
         char* red = nullptr;
-        FMI_COMM_RC(c->scratch(9 + 4 * j, padded * esz, s, &staging));
+        FMI_COMM_RC(c->scratch(chunk_slot(j, kStaging), sb * N, s, &staging));
         if (k >= 2) FMI_COMM_HIP(hipStreamWaitEvent(s, p.gathered[j], 0));  // chunk k - 2 has read red[j]
-        FMI_COMM_RC(c->scratch(10 + 4 * j, shard * esz, s, &red));
-        FMI_COMM_RC(c->t->all_to_all(src, staging, shard * esz, s));
-        std::vector<const void*> parts(N);
-        for (int r = 0; r < N; ++r) parts[r] = staging + r * shard * esz;
+        FMI_COMM_RC(c->scratch(chunk_slot(j, kReduced), sb, s, &red));
+        FMI_COMM_RC(shards_in(c, g, src, sb, cn * esz, false, chunk_slot(j, kPadIn), staging, sb, s));
+        const auto parts = shard_parts(g, staging, sb);
         FMI_COMM_RC(c->timing.begin(s));
-        FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, shard, s));
+        FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, g.shard, s));
         FMI_COMM_RC(c->timing.end(s));
         FMI_COMM_HIP(hipEventRecord(p.reduced[j], s));
         FMI_COMM_HIP(hipStreamWaitEvent(p.gs, p.reduced[j], 0));
-        if (padded == cn) {
-            FMI_COMM_RC(tg->all_gather(red, dst, shard * esz, p.gs));
-        } else {
-            char* out = nullptr;
-            FMI_COMM_RC(c->scratch(11 + 4 * j, padded * esz, p.gs, &out));
-            FMI_COMM_RC(tg->all_gather(red, out, shard * esz, p.gs));
-            FMI_COMM_RC(device_copy(dst, out, cn * esz, p.gs));
-        }
+        FMI_COMM_RC(shards_out(c, g, Back::kToAll, 0, *tg, p.gs, red, dst, sb, cn * esz, false, chunk_slot(j, kPadOut)));
         FMI_COMM_HIP(hipEventRecord(p.gathered[j], p.gs));
     }
     // the caller's stream sees the whole result
@@ -1632,10 +1714,7 @@ int allreduce_device(Comm* c, int op, int dtype, int kd, int alg, int path, cons
                      hipStream_t s) {
     const int N = c->t->n();
     const size_t esz = dtype_size(dtype);
-    if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE)) {  // reference P = 1: a copy
-        if (send != recv) FMI_COMM_RC(device_copy(recv, send, n * esz, s));
-        return FMI_OK;
-    }
+    if (one_rank(*c->t)) return one_rank_copy(send, recv, n * esz, s);
     // Float max / min: every peer of the reference allreduce keeps its own operand order, so on ±0 ties
     // and NaNs the peers' results differ. Each shard owner then computes the shard in every rank's order
     // and an all-to-all (instead of the all-gather) hands rank r the versions in its order. Same exchange
@@ -1658,79 +1737,55 @@ int allreduce_device(Comm* c, int op, int dtype, int kd, int alg, int path, cons
             if (rc != FMI_ERR_UNSUPPORTED) return rc;
         }
     }
-    const size_t shard = shard_elems(n, N);
-    const size_t padded = shard * N;
-    if (padded != n && path == FMI_PATH_TREE && !per_rank && c->t->ragged()) {
-        // no zero-padded copies in or out: the last shards are short (or empty) and move at their length
-        char* staging = nullptr;
-        char* red = nullptr;
-        FMI_COMM_RC(c->scratch(1, padded * esz, s, &staging));
-        FMI_COMM_RC(c->scratch(2, shard * esz, s, &red));
-        FMI_COMM_RC(c->t->all_to_all_ragged(static_cast<const char*>(send), staging, shard * esz, n * esz, s));
-        const size_t len = Transport::span(c->t->rank(), shard, n);  // elements of my shard
-        if (len) {
-            std::vector<const void*> parts(N);
-            for (int j = 0; j < N; ++j) parts[j] = staging + j * shard * esz;
-            FMI_COMM_RC(c->timing.begin(s));
-            FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, len, s));
-            FMI_COMM_RC(c->timing.end(s));
-        }
-        return c->t->all_gather_ragged(red, static_cast<char*>(recv), shard * esz, n * esz, s);
-    }
-    const char* src = nullptr;
-    FMI_COMM_RC(padded_source(c, n, padded, esz, send, s, &src));
+    const ShardGrid g(*c->t, n);
+    const size_t shard = g.shard, sb = shard * esz, nb = n * esz;
+    // ragged: no zero-padded copies in or out, the last shards are short (or empty) and move at their length
+    const bool ragged = g.ragged(path == FMI_PATH_TREE && !per_rank);
     // skewed (shard_stride): the shard kernel's N inputs and its output carved from one scratch range, each in its
     // own 4 KiB slot (a carved group); otherwise the inputs back to back and the output apart
-    const size_t stride = path != FMI_PATH_RCCL && !per_rank ? shard_stride(*c->t, shard * esz) : shard * esz;
-    const bool skewed = stride != shard * esz;
+    const size_t stride = path != FMI_PATH_RCCL && !per_rank && !ragged ? shard_stride(*c->t, sb) : sb;
+    const bool skewed = stride != sb;
     char* red = nullptr;
     char* staging = nullptr;
     if (skewed) {
-        FMI_COMM_RC(c->scratch(1, (static_cast<size_t>(N) + 1) * stride, s, &staging));
+        FMI_COMM_RC(c->scratch(kStaging, (static_cast<size_t>(N) + 1) * stride, s, &staging));
         red = staging + static_cast<size_t>(N) * stride;
     } else {
-        FMI_COMM_RC(c->scratch(2, (per_rank ? padded : shard) * esz, s, &red));
+        FMI_COMM_RC(c->scratch(kReduced, per_rank ? sb * N : sb, s, &red));
     }
     if (path != FMI_PATH_RCCL) {
-        if (!skewed) FMI_COMM_RC(c->scratch(1, padded * esz, s, &staging));
-        FMI_COMM_RC(c->t->all_to_all_strided(src, staging, shard * esz, stride, s));
-        std::vector<const void*> parts(N);
-        for (int j = 0; j < N; ++j) parts[j] = staging + j * stride;
+        if (!skewed) FMI_COMM_RC(c->scratch(kStaging, sb * N, s, &staging));
+        FMI_COMM_RC(shards_in(c, g, send, sb, nb, ragged, kPadIn, staging, stride, s));
+        const auto parts = shard_parts(g, staging, stride);
         if (per_rank) {
             FMI_COMM_RC(c->timing.begin(s));
             if (N >= 2 && N <= sched::kMaxFusedPeers && fused_covers(op, dtype, FMI_ALG_ALLREDUCE, N)) {
                 PeerPtrs ptrs{};
                 for (int j = 0; j < N; ++j) {
                     ptrs.in[j] = parts[j];
-                    ptrs.out[j] = red + j * shard * esz;
+                    ptrs.out[j] = red + j * sb;
                 }
                 FMI_COMM_RC(launch_fused_all_ranks(op, dtype, N, ptrs, shard, s));
             } else {
                 for (int r = 0; r < N; ++r)
-                    FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red + r * shard * esz, parts.data(), N, r, shard, s));
+                    FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red + r * sb, parts.data(), N, r, shard, s));
             }
             FMI_COMM_RC(c->timing.end(s));
-            if (padded == n) return c->t->all_to_all(red, static_cast<char*>(recv), shard * esz, s);
-            char* out = nullptr;
-            FMI_COMM_RC(c->scratch(3, padded * esz, s, &out));
-            FMI_COMM_RC(c->t->all_to_all(red, out, shard * esz, s));
-            FMI_COMM_RC(device_copy(recv, out, n * esz, s));
-            return FMI_OK;
+            return shards_out(c, g, Back::kTransposed, 0, *c->t, s, red, recv, sb, nb, false, kPadOut);
         }
-        FMI_COMM_RC(c->timing.begin(s));
-        FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, shard, s));
-        FMI_COMM_RC(c->timing.end(s));
+        if (const size_t len = ragged ? g.len : shard) {
+            FMI_COMM_RC(c->timing.begin(s));
+            FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, 0, len, s));
+            FMI_COMM_RC(c->timing.end(s));
+        }
     } else {
         // a mean: RCCL's own reduce-scatter with SUM, the shard scaled by fl(1 / N), then the all-gather below
+        const char* src = nullptr;
+        FMI_COMM_RC(padded_source(c, g, send, sb, nb, kPadIn, s, &src));
         FMI_COMM_RC(c->t->reduce_scatter(op == FMI_OP_AVG ? FMI_OP_SUM : op, dtype, src, red, shard, s));
         if (op == FMI_OP_AVG) FMI_COMM_RC(launch_mean_scale(dtype, red, shard, N, s));
     }
-    if (padded == n) return c->t->all_gather(red, static_cast<char*>(recv), shard * esz, s);
-    char* out = nullptr;
-    FMI_COMM_RC(c->scratch(3, padded * esz, s, &out));
-    FMI_COMM_RC(c->t->all_gather(red, out, shard * esz, s));
-    FMI_COMM_RC(device_copy(recv, out, n * esz, s));
-    return FMI_OK;
+    return shards_out(c, g, Back::kToAll, 0, *c->t, s, red, recv, sb, nb, ragged, kPadOut);
 }
 
 // fmi_comm_allreduce_scaled (include/fmi_dev.h): the sharded allreduce on path TREE, unpipelined, over scaled 8-bit
@@ -1740,42 +1795,30 @@ int allreduce_device(Comm* c, int op, int dtype, int kd, int alg, int path, cons
 int allreduce_scaled_device(Comm* c, int dtype, int alg, int out_dtype, const void* send, const float* in_scale, void* recv,
                             const float* out_scale, float* amax, size_t n, hipStream_t s) {
     const int N = c->t->n();
-    if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE))  // the P = 1 form: not a copy
+    if (one_rank(*c->t))  // the P = 1 form: not a copy
         return reduce_tree_scaled(dtype, alg, out_dtype, recv, &send, in_scale, out_scale, amax, 1, 0, n, s);
     const size_t osz = dtype_size(out_dtype);  // the inputs' element size is 1
-    const size_t shard = shard_elems(n, N);
-    const size_t padded = shard * N;
+    const ShardGrid g(*c->t, n);
     char* words = nullptr;
-    FMI_COMM_RC(c->scratch(18, (2 * static_cast<size_t>(N) + 1) * sizeof(float), s, &words));
+    FMI_COMM_RC(c->scratch(kScaledWords, (2 * static_cast<size_t>(N) + 1) * sizeof(float), s, &words));
     float* scales = reinterpret_cast<float*>(words);
     uint32_t* shard_amax = reinterpret_cast<uint32_t*>(words) + N;
     uint32_t* mine = shard_amax + N;
     FMI_COMM_RC(c->t->all_gather(reinterpret_cast<const char*>(in_scale), words, sizeof(float), s));
     if (amax) FMI_COMM_HIP(hipMemsetAsync(mine, 0, sizeof(uint32_t), s));
-    const char* src = nullptr;
-    FMI_COMM_RC(padded_source(c, n, padded, 1, send, s, &src));
     char* staging = nullptr;
     char* red = nullptr;
-    FMI_COMM_RC(c->scratch(1, padded, s, &staging));
-    FMI_COMM_RC(c->scratch(2, shard * osz, s, &red));
-    FMI_COMM_RC(c->t->all_to_all(src, staging, shard, s));
-    const size_t len = Transport::span(c->t->rank(), shard, n);  // elements of my shard
-    if (len) {
-        std::vector<const void*> parts(N);
-        for (int j = 0; j < N; ++j) parts[j] = staging + j * shard;
+    FMI_COMM_RC(c->scratch(kStaging, g.shard * N, s, &staging));
+    FMI_COMM_RC(c->scratch(kReduced, g.shard * osz, s, &red));
+    FMI_COMM_RC(shards_in(c, g, send, g.shard, n, false, kPadIn, staging, g.shard, s));
+    if (g.len) {
+        const auto parts = shard_parts(g, staging, g.shard);
         FMI_COMM_RC(c->timing.begin(s));
         FMI_COMM_RC(reduce_tree_scaled(dtype, alg, out_dtype, red, parts.data(), scales, out_scale,
-                                       amax ? reinterpret_cast<float*>(mine) : nullptr, N, 0, len, s));
+                                       amax ? reinterpret_cast<float*>(mine) : nullptr, N, 0, g.len, s));
         FMI_COMM_RC(c->timing.end(s));
     }
-    if (padded == n) {
-        FMI_COMM_RC(c->t->all_gather(red, static_cast<char*>(recv), shard * osz, s));
-    } else {
-        char* out = nullptr;
-        FMI_COMM_RC(c->scratch(3, padded * osz, s, &out));
-        FMI_COMM_RC(c->t->all_gather(red, out, shard * osz, s));
-        FMI_COMM_RC(device_copy(recv, out, n * osz, s));
-    }
+    FMI_COMM_RC(shards_out(c, g, Back::kToAll, 0, *c->t, s, red, recv, g.shard * osz, n * osz, false, kPadOut));
     if (amax) {
         // every owner's shard amax, then one fold with what *amax held: the same word on every rank
         FMI_COMM_RC(c->t->all_gather(reinterpret_cast<const char*>(mine), reinterpret_cast<char*>(shard_amax), sizeof(uint32_t), s));
@@ -1792,73 +1835,53 @@ int allreduce_scaled_device(Comm* c, int dtype, int alg, int out_dtype, const vo
 int allreduce_mx_device(Comm* c, int op, int dtype, int alg, int out_dtype, const void* send, const void* send_scales,
                         void* recv, void* recv_scales, size_t n, hipStream_t s, const uint64_t* seed = nullptr, uint64_t first = 0) {
     const int N = c->t->n();
-    if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE))  // the P = 1 form: not a copy
+    if (one_rank(*c->t))  // the P = 1 form: not a copy
         return reduce_tree_mx(op, dtype, alg, out_dtype, recv, recv_scales, &send, &send_scales, 1, 0, n, s, seed, first);
     static_assert(kShardAlign % 32 == 0, "shard boundaries are MX block (and so FP4 byte) boundaries");
     const bool wide = out_dtype == FMI_F32;
     // Byte counts: eb per input shard (shard for the 8-bit floats; shard / 2 for FMI_F4E2M1, whole bytes and whole
     // blocks because kShardAlign is even), ob per output shard, nb / nob for the buckets' first n elements. Only the last
     // non-empty shard can have an odd TRUE length, and its kernel writes that byte's high nibble as 0.
-    const size_t shard = shard_elems(n, N);
+    const ShardGrid g(*c->t, n);
+    const size_t shard = g.shard;
     const size_t eb = mx_elem_bytes(dtype, shard), ob = wide ? shard * sizeof(float) : eb;
     const size_t nb = mx_elem_bytes(dtype, n), nob = wide ? n * sizeof(float) : nb;
-    const bool ragged = shard * N != n;
-    const size_t nsc = (n + 31) / 32, sshard = shard / 32, spadded = sshard * N;
-    const char* src = nullptr;
-    FMI_COMM_RC(padded_source(c, nb, eb * N, 1, send, s, &src));
-    const char* ssrc = static_cast<const char*>(send_scales);
-    if (spadded != nsc) {
-        char* pad = nullptr;
-        FMI_COMM_RC(c->scratch(19, spadded, s, &pad));
-        FMI_COMM_HIP(hipMemcpyAsync(pad, send_scales, nsc, hipMemcpyDeviceToDevice, s));
-        FMI_COMM_HIP(hipMemsetAsync(pad + nsc, 0, spadded - nsc, s));
-        ssrc = pad;
-    }
+    const size_t nsc = (n + 31) / 32, sshard = shard / 32;
     char *staging = nullptr, *red = nullptr, *sstaging = nullptr, *sred = nullptr;
-    FMI_COMM_RC(c->scratch(1, eb * N, s, &staging));
-    FMI_COMM_RC(c->scratch(2, ob, s, &red));
-    FMI_COMM_RC(c->scratch(20, spadded, s, &sstaging));
-    FMI_COMM_RC(c->scratch(21, sshard, s, &sred));
-    FMI_COMM_RC(c->t->all_to_all(src, staging, eb, s));
-    FMI_COMM_RC(c->t->all_to_all(ssrc, sstaging, sshard, s));
-    const size_t len = Transport::span(c->t->rank(), shard, n);  // elements of my shard
-    if (len) {
-        std::vector<const void*> parts(N), sparts(N);
-        for (int j = 0; j < N; ++j) parts[j] = staging + j * eb, sparts[j] = sstaging + j * sshard;
+    FMI_COMM_RC(c->scratch(kStaging, eb * N, s, &staging));
+    FMI_COMM_RC(c->scratch(kReduced, ob, s, &red));
+    FMI_COMM_RC(c->scratch(kMxScaleStaging, sshard * N, s, &sstaging));
+    FMI_COMM_RC(c->scratch(kMxScaleReduced, sshard, s, &sred));
+    FMI_COMM_RC(shards_in(c, g, send, eb, nb, false, kPadIn, staging, eb, s));
+    FMI_COMM_RC(shards_in(c, g, send_scales, sshard, nsc, false, kMxScalePadIn, sstaging, sshard, s));
+    if (g.len) {
+        const auto parts = shard_parts(g, staging, eb), sparts = shard_parts(g, sstaging, sshard);
         FMI_COMM_RC(c->timing.begin(s));
-        FMI_COMM_RC(reduce_tree_mx(op, dtype, alg, out_dtype, red, sred, parts.data(), sparts.data(), N, 0, len, s, seed,
-                                   first + static_cast<uint64_t>(c->t->rank()) * shard));
+        FMI_COMM_RC(reduce_tree_mx(op, dtype, alg, out_dtype, red, sred, parts.data(), sparts.data(), N, 0, g.len, s, seed,
+                                   first + static_cast<uint64_t>(g.rank) * shard));
         FMI_COMM_RC(c->timing.end(s));
     }
-    if (!ragged) {
-        FMI_COMM_RC(c->t->all_gather(red, static_cast<char*>(recv), ob, s));
-    } else {
-        char* out = nullptr;
-        FMI_COMM_RC(c->scratch(3, ob * N, s, &out));
-        FMI_COMM_RC(c->t->all_gather(red, out, ob, s));
-        FMI_COMM_RC(device_copy(recv, out, nob, s));
-    }
+    FMI_COMM_RC(shards_out(c, g, Back::kToAll, 0, *c->t, s, red, recv, ob, nob, false, kPadOut));
     if (wide) return FMI_OK;
-    if (spadded == nsc) {
-        FMI_COMM_RC(c->t->all_gather(sred, static_cast<char*>(recv_scales), sshard, s));
-    } else {
-        char* out = nullptr;
-        FMI_COMM_RC(c->scratch(22, spadded, s, &out));
-        FMI_COMM_RC(c->t->all_gather(sred, out, sshard, s));
-        FMI_COMM_HIP(hipMemcpyAsync(recv_scales, out, nsc, hipMemcpyDeviceToDevice, s));
-    }
-    return FMI_OK;
+    return shards_out(c, g, Back::kToAll, 0, *c->t, s, sred, recv_scales, sshard, nsc, false, kMxScalePadOut);
 }
 
 int comm_init(fmi_comm_t* comm, const void* id, int nranks, int rank, double timeout_s);
 
-int check_allreduce_args(int alg, int path) {
+// dtype, kd: as check_common left them.
+int check_allreduce_args(int alg, int path, int dtype, int kd) {
     if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE_LTR)
         return fail(FMI_ERR_INVALID, "allreduce: alg must be ALLREDUCE or REDUCE_LTR");
     if (path != FMI_PATH_TREE && path != FMI_PATH_RCCL && path != FMI_PATH_DIRECT)
         return fail(FMI_ERR_INVALID, "unknown path");
     if (path == FMI_PATH_RCCL && alg != FMI_ALG_ALLREDUCE)
         return fail(FMI_ERR_INVALID, "ordered (LTR) allreduce needs the tree path");
+    if (path == FMI_PATH_RCCL && is_fp8_dtype(dtype))
+        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: the 8-bit float dtypes need path TREE or DIRECT (RCCL's reduction has its "
+                                         "own order and rounding)");
+    if (path == FMI_PATH_RCCL && accumulates_f32(kd))
+        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: FMI_ACC_F32 needs path TREE or DIRECT (RCCL's reduction has its own order "
+                                         "and rounding)");
     return FMI_OK;
 }
 
@@ -2077,13 +2100,7 @@ static int comm_allreduce_impl(fmi_comm_t comm, int op, int dtype, int alg, int 
                        fmi_stream_t stream) {
     int kd = 0;  // the shard step's dtype argument (check_common)
     FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
-    FMI_COMM_RC(check_allreduce_args(alg, path));
-    if (path == FMI_PATH_RCCL && is_fp8_dtype(dtype))
-        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: the 8-bit float dtypes need path TREE or DIRECT (RCCL's reduction has its "
-                                         "own order and rounding)");
-    if (path == FMI_PATH_RCCL && accumulates_f32(kd))
-        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: FMI_ACC_F32 needs path TREE or DIRECT (RCCL's reduction has its own order "
-                                         "and rounding)");
+    FMI_COMM_RC(check_allreduce_args(alg, path, dtype, kd));
     if (n == 0) return FMI_OK;
     if (!send || !recv) return fail(FMI_ERR_INVALID, "null bucket");
     Comm* c = static_cast<Comm*>(comm);
@@ -2098,9 +2115,7 @@ static int comm_allreduce_scaled_impl(fmi_comm_t comm, int op, int dtype_arg, in
     FMI_COMM_RC(scaled_check_args("fmi_comm_allreduce_scaled", op, dtype_arg, alg, out_dtype, &dtype));
     if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE_LTR)
         return fail(FMI_ERR_INVALID, "fmi_comm_allreduce_scaled: alg must be ALLREDUCE or REDUCE_LTR");
-    if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
-    if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
-    if (static_cast<Comm*>(comm)->t->aborted()) return aborted_error();
+    FMI_COMM_RC(check_ready(comm));
     if (n == 0) return FMI_OK;
     if (!send || !recv || !in_scale) return fail(FMI_ERR_INVALID, "null bucket");
     Comm* c = static_cast<Comm*>(comm);
@@ -2121,9 +2136,7 @@ static int comm_allreduce_mx_impl(fmi_comm_t comm, int op, int dtype_arg, int al
     }
     if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE_LTR)
         return fail(FMI_ERR_INVALID, std::string(who) + ": alg must be ALLREDUCE or REDUCE_LTR");
-    if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
-    if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
-    if (static_cast<Comm*>(comm)->t->aborted()) return aborted_error();
+    FMI_COMM_RC(check_ready(comm));
     if (n == 0) return FMI_OK;
     if (!send || !recv || !send_scales) return fail(FMI_ERR_INVALID, "null bucket");
     Comm* c = static_cast<Comm*>(comm);
@@ -2139,13 +2152,7 @@ static int comm_allreduce_host_impl(fmi_comm_t comm, int op, int dtype, int alg,
                             size_t n, size_t chunk) {
     int kd = 0;  // the shard step's dtype argument (check_common)
     FMI_COMM_RC(check_common(comm, op, &dtype, &kd));
-    FMI_COMM_RC(check_allreduce_args(alg, path));
-    if (path == FMI_PATH_RCCL && is_fp8_dtype(dtype))
-        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: the 8-bit float dtypes need path TREE or DIRECT (RCCL's reduction has its "
-                                         "own order and rounding)");
-    if (path == FMI_PATH_RCCL && accumulates_f32(kd))
-        return fail(FMI_ERR_UNSUPPORTED, "path RCCL: FMI_ACC_F32 needs path TREE or DIRECT (RCCL's reduction has its own order "
-                                         "and rounding)");
+    FMI_COMM_RC(check_allreduce_args(alg, path, dtype, kd));
     if (n == 0) return FMI_OK;
     if (!send || !recv) return fail(FMI_ERR_INVALID, "null bucket");
     Comm* c = static_cast<Comm*>(comm);
@@ -2161,7 +2168,7 @@ static int comm_allreduce_host_impl(fmi_comm_t comm, int op, int dtype, int alg,
     }
     chunk = std::min(chunk, n);
     const size_t nchunks = (n + chunk - 1) / chunk;
-    static constexpr int kIn[HostPipe::kDepth] = {4, 5, 16}, kOut[HostPipe::kDepth] = {6, 7, 17};  // Comm scratch slots
+    static constexpr Slot kIn[HostPipe::kDepth] = {kHostIn0, kHostIn1, kHostIn2}, kOut[HostPipe::kDepth] = {kHostOut0, kHostOut1, kHostOut2};
     char* in[HostPipe::kDepth] = {};
     char* out[HostPipe::kDepth] = {};
     for (int j = 0; j < D && static_cast<size_t>(j) < nchunks; ++j) {
@@ -2215,35 +2222,18 @@ static int comm_reduce_impl(fmi_comm_t comm, int op, int dtype, int alg, const v
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t s = resolve_stream(stream);
     const size_t esz = dtype_size(dtype);
-    if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE)) {
-        if (send != recv) FMI_COMM_RC(device_copy(recv, send, n * esz, s));
-        return FMI_OK;
-    }
-    const size_t shard = shard_elems(n, N);
-    const size_t padded = shard * N;
-    const bool is_root = c->t->rank() == root;
+    if (one_rank(*c->t)) return one_rank_copy(send, recv, n * esz, s);
+    const ShardGrid g(*c->t, n);
+    const size_t sb = g.shard * esz;
+    const bool ragged = g.ragged(true);  // short last shards at their own length: no padded copies
     char* staging = nullptr;
     char* red = nullptr;
-    FMI_COMM_RC(c->scratch(1, padded * esz, s, &staging));
-    FMI_COMM_RC(c->scratch(2, shard * esz, s, &red));
-    std::vector<const void*> parts(N);
-    for (int j = 0; j < N; ++j) parts[j] = staging + j * shard * esz;
-    if (padded != n && c->t->ragged()) {  // short last shards at their own length: no padded copies
-        FMI_COMM_RC(c->t->all_to_all_ragged(static_cast<const char*>(send), staging, shard * esz, n * esz, s));
-        const size_t len = Transport::span(c->t->rank(), shard, n);
-        FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, root, len, s));
-        return c->t->gather_ragged(red, is_root ? static_cast<char*>(recv) : nullptr, shard * esz, n * esz, root, s);
-    }
-    const char* src = nullptr;
-    FMI_COMM_RC(padded_source(c, n, padded, esz, send, s, &src));
-    FMI_COMM_RC(c->t->all_to_all(src, staging, shard * esz, s));
-    FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, root, shard, s));
-    if (padded == n) return c->t->gather(red, is_root ? static_cast<char*>(recv) : nullptr, shard * esz, root, s);
-    char* out = nullptr;
-    FMI_COMM_RC(c->scratch(3, padded * esz, s, &out));
-    FMI_COMM_RC(c->t->gather(red, out, shard * esz, root, s));
-    if (is_root) FMI_COMM_RC(device_copy(recv, out, n * esz, s));
-    return FMI_OK;
+    FMI_COMM_RC(c->scratch(kStaging, sb * N, s, &staging));
+    FMI_COMM_RC(c->scratch(kReduced, sb, s, &red));
+    FMI_COMM_RC(shards_in(c, g, send, sb, n * esz, ragged, kPadIn, staging, sb, s));
+    const auto parts = shard_parts(g, staging, sb);
+    FMI_COMM_RC(fmi_dev_reduce_tree(op, kd, alg, red, parts.data(), N, root, ragged ? g.len : g.shard, s));
+    return shards_out(c, g, Back::kToRoot, root, *c->t, s, red, g.rank == root ? recv : nullptr, sb, n * esz, ragged, kPadOut);
 }
 
 // The reference's reduce with its side effect on every sendbuf (PeerToPeer.cpp:59-84): all-to-all of shards
@@ -2267,42 +2257,26 @@ static int comm_reduce_sendbuf_impl(fmi_comm_t comm, int op, int dtype, int alg,
     hipStream_t s = resolve_stream(stream);
     const size_t esz = dtype_size(dtype);
     const bool is_root = c->t->rank() == root;
-    if (N > 1 || tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE)) {
-        const size_t shard = shard_elems(n, N);
-        const size_t padded = shard * N;
-        const bool ragged = padded != n && c->t->ragged();  // short last shards at their own length
+    if (!one_rank(*c->t)) {
+        const ShardGrid g(*c->t, n);
+        const size_t sb = g.shard * esz;
+        const bool ragged = g.ragged(true);  // short last shards at their own length
         char* staging = nullptr;
         char* partial = nullptr;
-        FMI_COMM_RC(c->scratch(1, padded * esz, s, &staging));
-        FMI_COMM_RC(c->scratch(2, padded * esz, s, &partial));
-        if (ragged) {
-            FMI_COMM_RC(c->t->all_to_all_ragged(static_cast<const char*>(send), staging, shard * esz, n * esz, s));
-        } else {
-            const char* src = nullptr;
-            FMI_COMM_RC(padded_source(c, n, padded, esz, send, s, &src));
-            FMI_COMM_RC(c->t->all_to_all(src, staging, shard * esz, s));
-        }
+        FMI_COMM_RC(c->scratch(kStaging, sb * N, s, &staging));
+        FMI_COMM_RC(c->scratch(kReduced, sb * N, s, &partial));
+        FMI_COMM_RC(shards_in(c, g, send, sb, n * esz, ragged, kPadIn, staging, sb, s));
         // transformed id t = (rank - root) mod N (PeerToPeer.cpp:287-293): input t is real rank (t + root) % N,
         // and output t goes to the block of that real rank (the all-to-all back delivers block j to rank j)
         std::vector<const void*> ins(N);
         std::vector<void*> outs(N);
         for (int t = 0; t < N; ++t) {
             const int real = (t + root) % N;
-            ins[t] = staging + real * shard * esz;
-            outs[t] = partial + real * shard * esz;
+            ins[t] = staging + real * sb;
+            outs[t] = partial + real * sb;
         }
-        const size_t len = ragged ? Transport::span(c->t->rank(), shard, n) : shard;
-        FMI_COMM_RC(reduce_partials(op, kd, outs.data(), ins.data(), N, len, s));
-        if (ragged) {
-            FMI_COMM_RC(c->t->all_to_all_back_ragged(partial, static_cast<char*>(send), shard * esz, n * esz, s));
-        } else if (padded == n) {
-            FMI_COMM_RC(c->t->all_to_all(partial, static_cast<char*>(send), shard * esz, s));
-        } else {
-            char* out = nullptr;
-            FMI_COMM_RC(c->scratch(3, padded * esz, s, &out));
-            FMI_COMM_RC(c->t->all_to_all(partial, out, shard * esz, s));
-            FMI_COMM_RC(device_copy(send, out, n * esz, s));
-        }
+        FMI_COMM_RC(reduce_partials(op, kd, outs.data(), ins.data(), N, ragged ? g.len : g.shard, s));
+        FMI_COMM_RC(shards_out(c, g, Back::kTransposed, 0, *c->t, s, partial, send, sb, n * esz, ragged, kPadOut));
     }
     if (is_root && recv != send) FMI_COMM_RC(device_copy(recv, send, n * esz, s));
     return FMI_OK;
@@ -2320,47 +2294,27 @@ static int comm_scan_impl(fmi_comm_t comm, int op, int dtype, int alg, const voi
     hipStream_t s = resolve_stream(stream);
     const int N = c->t->n();
     const size_t esz = dtype_size(dtype);
-    if (N == 1 && !tune(FMI_TUNE_COMM_ONE_RANK_EXCHANGE)) {
-        if (send != recv) FMI_COMM_RC(device_copy(recv, send, n * esz, s));
-        return FMI_OK;
-    }
-    const size_t shard = shard_elems(n, N);
-    const size_t padded = shard * N;
+    if (one_rank(*c->t)) return one_rank_copy(send, recv, n * esz, s);
+    const ShardGrid g(*c->t, n);
+    const size_t sb = g.shard * esz;
+    const bool ragged = g.ragged(true);  // short last shards at their own length: no padded copies
     char* staging = nullptr;
     char* prefix = nullptr;
-    FMI_COMM_RC(c->scratch(1, padded * esz, s, &staging));
-    FMI_COMM_RC(c->scratch(2, padded * esz, s, &prefix));
-    std::vector<const void*> ins(N);
+    FMI_COMM_RC(c->scratch(kStaging, sb * N, s, &staging));
+    FMI_COMM_RC(c->scratch(kReduced, sb * N, s, &prefix));
+    const auto ins = shard_parts(g, staging, sb);
     std::vector<void*> outs(N);
-    for (int j = 0; j < N; ++j) {
-        ins[j] = staging + j * shard * esz;
-        outs[j] = prefix + j * shard * esz;  // prefix of rank j over my shard
-    }
-    if (padded != n && c->t->ragged()) {  // short last shards at their own length: no padded copies
-        FMI_COMM_RC(c->t->all_to_all_ragged(static_cast<const char*>(send), staging, shard * esz, n * esz, s));
-        const size_t len = Transport::span(c->t->rank(), shard, n);
-        FMI_COMM_RC(fmi_dev_scan_peers(op, kd, alg, outs.data(), ins.data(), N, len, s));
-        return c->t->all_to_all_back_ragged(prefix, static_cast<char*>(recv), shard * esz, n * esz, s);
-    }
-    const char* src = nullptr;
-    FMI_COMM_RC(padded_source(c, n, padded, esz, send, s, &src));
-    FMI_COMM_RC(c->t->all_to_all(src, staging, shard * esz, s));
-    FMI_COMM_RC(fmi_dev_scan_peers(op, kd, alg, outs.data(), ins.data(), N, shard, s));
+    for (int j = 0; j < N; ++j) outs[j] = prefix + j * sb;  // prefix of rank j over my shard
+    FMI_COMM_RC(shards_in(c, g, send, sb, n * esz, ragged, kPadIn, staging, sb, s));
+    FMI_COMM_RC(fmi_dev_scan_peers(op, kd, alg, outs.data(), ins.data(), N, ragged ? g.len : g.shard, s));
     // rank k gathers its prefix shard j from rank j: an all-to-all back
-    if (padded == n) return c->t->all_to_all(prefix, static_cast<char*>(recv), shard * esz, s);
-    char* out = nullptr;
-    FMI_COMM_RC(c->scratch(3, padded * esz, s, &out));
-    FMI_COMM_RC(c->t->all_to_all(prefix, out, shard * esz, s));
-    FMI_COMM_RC(device_copy(recv, out, n * esz, s));
-    return FMI_OK;
+    return shards_out(c, g, Back::kTransposed, 0, *c->t, s, prefix, recv, sb, n * esz, ragged, kPadOut);
 }
 
-#define FMI_COMM_PRELUDE()                                                        \
-    if (!comm) return fail(FMI_ERR_INVALID, "null communicator");                 \
-    if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called"); \
-    Comm* c = static_cast<Comm*>(comm);                                           \
-    std::lock_guard<std::mutex> lk(c->mu);                                        \
-    if (c->t->aborted()) return aborted_error();                                  \
+#define FMI_COMM_PRELUDE()                 \
+    std::unique_lock<std::mutex> lk;       \
+    FMI_COMM_RC(check_ready(comm, &lk));   \
+    Comm* c = static_cast<Comm*>(comm);    \
     hipStream_t s = resolve_stream(stream);
 
 static int comm_bcast_impl(fmi_comm_t comm, void* buf, size_t bytes, int root, fmi_stream_t stream) {
@@ -2501,12 +2455,9 @@ int fmi_comm_unique_id(int transport, void* id, size_t len) {
 
 int fmi_comm_sync(fmi_comm_t comm, fmi_stream_t stream) {
     return guarded("fmi_comm_sync", [&]() -> int {
-        if (!comm) return fail(FMI_ERR_INVALID, "null communicator");
-        if (!library_stream()) return fail(FMI_ERR_NO_DEVICE, "fmi_dev_init has not been called");
-        Comm* c = static_cast<Comm*>(comm);
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (c->t->aborted()) return aborted_error();
-        return c->t->wait_stream(resolve_stream(stream), "fmi_comm_sync");
+        std::unique_lock<std::mutex> lk;
+        FMI_COMM_RC(check_ready(comm, &lk));
+        return static_cast<Comm*>(comm)->t->wait_stream(resolve_stream(stream), "fmi_comm_sync");
     });
 }
 

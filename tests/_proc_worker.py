@@ -46,6 +46,14 @@ def run(c, N, r):
         c.scan(op, s, o)
         fmi_amd.sync()
         out["scan_" + np.dtype(dtype).name] = o.numpy()
+    # the sendbuf reduce at the same ragged length: this transport pads, so the partials come back through scratch
+    s = Bucket.from_numpy(inputs(np.float32, 65536 + 129, r, seed=38))
+    o = Bucket(65536 + 129, np.float32) if r == N - 1 else None
+    c.reduce(Op.SUM, s, o, N - 1, sendbuf_partials=True)
+    fmi_amd.sync()
+    out["sendbuf_send"] = s.numpy()
+    if o is not None:
+        out["sendbuf_recv"] = o.numpy()
     # path DIRECT: windows exported with hipIpcGetMemHandle and mapped by every other process
     for dtype, op, n in ((np.float32, Op.SUM, 3 * 65536 + 5), (np.int32, Op.MIN, 1027)):
         w = c.window(n + 1, dtype)

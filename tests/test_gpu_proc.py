@@ -56,6 +56,10 @@ def test_proc_transport_collectives(device, N, tmp_path):
             want, _ = orc.scan([inputs(dtype, 65536 + 129, r, seed=34) for r in range(N)], orc.OPS[op])
             for r in range(N):
                 assert_bit_equal(res[r]["scan_" + np.dtype(dtype).name], want[r], f"scan {op} rank {r}")
+        want, sends = orc.reduce([inputs(np.float32, 65536 + 129, r, seed=38) for r in range(N)], orc.op_sum, root=N - 1)
+        for r in range(N):
+            assert_bit_equal(res[r]["sendbuf_send"], sends[r], f"sendbuf reduce root {N - 1}: sendbuf of rank {r}")
+        assert_bit_equal(res[N - 1]["sendbuf_recv"], want, f"sendbuf reduce root {N - 1} result")
         want, _ = orc.allreduce([inputs(np.float64, 3 * 4099 + 17, r, seed=36) for r in range(N)], orc.op_sum)
         for r in range(N):
             assert_bit_equal(res[r]["host_f64"], want[r], f"host allreduce rank {r}")
