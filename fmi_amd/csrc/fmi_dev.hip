@@ -25,11 +25,6 @@ struct DeviceState {
     size_t lds_per_cu = 160 * 1024;  // gfx950
     size_t lds_per_wg = 160 * 1024;
     hipStream_t stream = nullptr;
-    // scratch arena for the pairwise-pass execution of P-way programs; arena_free marks when the work
-    // that last used it has drained (the next user's stream waits on it)
-    void* arena = nullptr;
-    size_t arena_bytes = 0;
-    hipEvent_t arena_free = nullptr;
 };
 
 std::mutex g_mu;
@@ -184,6 +179,12 @@ int require_device() {
 hipStream_t resolve(fmi_stream_t s) { return s ? static_cast<hipStream_t>(s) : g_state.stream; }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// every a[p], and every b[p] where b is given
+bool all_aligned16(const void* const* a, void* const* b, int P) {
+    bool ok = true;
+    for (int p = 0; p < P; ++p) ok = ok && aligned16(a[p]) && (!b || aligned16(b[p]));
+    return ok;
+}
 
 // Is `p` page-locked host memory the device can address? Returns its device-side address.
 bool host_mapped_at(void* p, void** dev) {
@@ -281,87 +282,136 @@ int launch_combine(int op, int dtype, void* out, const void* a, const void* b, s
 }
 
 // ----------------------------------------------------------------------------------------------------
-// Scratch arena for P-way temporaries (caller holds g_mu). Stream s waits until the previous user's work
-// has drained; the caller records g_state.arena_free on s after its last launch touching the arena.
+// Library-owned temporaries: a grow-only device buffer with its own mutex and the event that marks when the work that
+// last used it has drained. A call takes one with a Lease, which holds the mutex while the call's launches are
+// enqueued: the stream waits until the previous user's work has drained before it touches the buffer, the buffer only
+// grows (freed and reallocated) under the lease and after that event has completed, and the event is recorded on the
+// stream when the lease ends, after the call's last launch, on every path out of its scope. So no call can free or
+// write a buffer that another call's enqueued work still uses, and none has to remember the record.
+// The temporaries are ordered by an event recorded outside any graph: a captured call would record the event inside
+// the graph, and its replays would write them unordered against later direct calls. So a capturing stream is refused.
+// Two objects exist, and a call that holds both takes them in this order, never the other: g_f32_temps, then g_arena
+// (the f32 bridge runs the library's own FMI_F32 program inside its lease, and that program may take the arena and
+// reallocate it, which is why the two are separate allocations). fmi_dev_finalize takes both, in that order.
 // ----------------------------------------------------------------------------------------------------
-// Temporaries of the library's own are ordered by an event recorded outside any graph: a captured call would record
-// the event inside the graph, and its replays would write them unordered against later direct calls.
-int refuse_capture(hipStream_t s, const char* needs) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    FMI_HIP_TRY(hipStreamIsCapturing(s, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return fail(FMI_ERR_UNSUPPORTED, std::string("this call needs ") + needs + " and cannot be captured in a graph");
-    return FMI_OK;
-}
+struct Scratch {
+    const char* const name;   // in the allocation failure texts
+    const char* const needs;  // what the refusal of a captured call says the call needs
+    std::mutex mu;
+    void* buf = nullptr;
+    size_t bytes = 0;
+    hipEvent_t drained = nullptr;
 
-int arena_acquire(size_t need, hipStream_t s) {
-    FMI_RC_TRY(refuse_capture(s, "the library's scratch arena (unaligned or 8/16-bit integer buckets, 8-bit float buckets "
-                                 "without FMI_ACC_F32, or a P-way program beyond the fused kernels)"));
-    if (!g_state.arena_free) FMI_HIP_TRY(hipEventCreateWithFlags(&g_state.arena_free, hipEventDisableTiming));
-    if (g_state.arena_bytes < need) {
-        FMI_HIP_TRY(hipEventSynchronize(g_state.arena_free));  // previous users have drained
-        if (g_state.arena) FMI_HIP_TRY(hipFree(g_state.arena));
-        g_state.arena = nullptr;
-        g_state.arena_bytes = 0;
-        const hipError_t e = hipMalloc(&g_state.arena, need);
-        if (e != hipSuccess) return fail(FMI_ERR_ALLOC, std::string("hipMalloc (P-way scratch): ") + hipGetErrorString(e));
-        g_state.arena_bytes = need;
+    // `count` slots of `stride` bytes on stream s. status() != FMI_OK: nothing is held and slot() must not be used.
+    class Lease {
+      public:
+        Lease(Scratch& sc, size_t stride, int count, hipStream_t s) : sc_(sc), lk_(sc.mu), stride_(stride), s_(s) {
+            rc_ = acquire(static_cast<size_t>(count));
+        }
+        ~Lease() { (void)record(); }
+        Lease(const Lease&) = delete;
+        Lease& operator=(const Lease&) = delete;
+        int status() const { return rc_; }
+        void* slot(int k) const { return static_cast<char*>(sc_.buf) + stride_ * static_cast<size_t>(k); }
+        // The end of the call's use, after its last launch: `body`, or the failure to record where the body succeeded.
+        int done(int body) {
+            const int rec = record();
+            return body != FMI_OK ? body : rec;
+        }
+
+      private:
+        int acquire(size_t count) {
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            FMI_HIP_TRY(hipStreamIsCapturing(s_, &cap));
+            if (cap != hipStreamCaptureStatusNone)
+                return fail(FMI_ERR_UNSUPPORTED, std::string("this call needs ") + sc_.needs + " and cannot be captured in a graph");
+            size_t need = 0;
+            if (__builtin_mul_overflow(stride_, count, &need)) return fail(FMI_ERR_ALLOC, std::string(sc_.name) + ": size overflows");
+            if (!sc_.drained) FMI_HIP_TRY(hipEventCreateWithFlags(&sc_.drained, hipEventDisableTiming));
+            if (sc_.bytes < need) {
+                FMI_HIP_TRY(hipEventSynchronize(sc_.drained));  // previous users have drained
+                if (sc_.buf) FMI_HIP_TRY(hipFree(sc_.buf));
+                sc_.buf = nullptr;
+                sc_.bytes = 0;
+                const hipError_t e = hipMalloc(&sc_.buf, need);
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();  // not left for the next launch's error check to find
+                    return fail(FMI_ERR_ALLOC, "hipMalloc(" + std::to_string(need) + ") for " + sc_.name + ": " + hipGetErrorString(e));
+                }
+                sc_.bytes = need;
+            }
+            FMI_HIP_TRY(hipStreamWaitEvent(s_, sc_.drained, 0));
+            held_ = true;
+            return FMI_OK;
+        }
+        int record() {
+            if (!held_) return FMI_OK;
+            held_ = false;
+            FMI_HIP_TRY(hipEventRecord(sc_.drained, s_));
+            return FMI_OK;
+        }
+        Scratch& sc_;
+        std::unique_lock<std::mutex> lk_;
+        const size_t stride_;
+        const hipStream_t s_;
+        bool held_ = false;
+        int rc_ = FMI_OK;
+    };
+
+    void release() {  // fmi_dev_finalize (holding mu), after the device has drained
+        if (buf) (void)hipFree(buf);
+        if (drained) (void)hipEventDestroy(drained);
+        buf = nullptr, bytes = 0, drained = nullptr;
     }
-    FMI_HIP_TRY(hipStreamWaitEvent(s, g_state.arena_free, 0));
-    return FMI_OK;
-}
+};
+// The P-way temporaries of the pairwise-pass and blocked programs.
+Scratch g_arena{"the P-way scratch arena",
+                "the library's scratch arena (unaligned or 8/16-bit integer buckets, 8-bit float buckets "
+                "without FMI_ACC_F32, or a P-way program beyond the fused kernels)"};
+// The f32 temporaries of the f32 bridge (FMI_ACC_F32 beyond the fused kernels, the scaled and MX calls beyond theirs).
+Scratch g_f32_temps{"the f32 temporaries", "f32 temporaries (FMI_ACC_F32 beyond 16 peers or on unaligned buckets)"};
 
 size_t arena_stride(size_t n, size_t esz) { return (std::max<size_t>(n * esz, 16) + 255) / 256 * 256; }
+
+// A launch's pointer table (PeerPtrs or BlockedScanPtrs): peer p's input in slot p, and with `outs` its output there
+// too. With a carry, slot 0 is the carry (an input alone) and peer p takes slot 1 + p.
+template <class Ptrs>
+Ptrs peer_table(const void* const* ins, void* const* outs, int P, const void* carry = nullptr) {
+    Ptrs t{};
+    const int first = carry ? 1 : 0;
+    if (carry) t.in[0] = carry;
+    for (int p = 0; p < P; ++p) {
+        t.in[first + p] = ins[p];
+        if (outs) t.out[first + p] = outs[p];
+    }
+    return t;
+}
+// ... for one result, which is slot 0's output.
+template <class Ptrs>
+Ptrs peer_table(const void* const* ins, int P, void* out, const void* carry = nullptr) {
+    Ptrs t = peer_table<Ptrs>(ins, nullptr, P, carry);
+    t.out[0] = out;
+    return t;
+}
 
 // ----------------------------------------------------------------------------------------------------
 // P-way programs for unaligned buckets and the byte/16-bit integer dtypes (fused_covers): the same
 // schedule, one pairwise pass per step. Only the steps the requested outputs depend on run (an allreduce
 // for one rank needs P - 1 of its P log P steps). Temp buckets live in the arena; slots are assigned on
-// the host (a value's slot is recycled right after its last use) so the arena holds only the peak number
-// of live temps.
+// the host (a value's slot is recycled right after its last use: sched::plan_stepwise) so the arena holds
+// only the peak number of live temps.
 // ----------------------------------------------------------------------------------------------------
 int run_program_stepwise(int op, int dtype, const sched::HostProgram& prog, void* const* outs, int nouts,
                          const int* out_value, const void* const* ins, size_t n, hipStream_t s) {
     const size_t esz = dtype_size(dtype);
     const int P = prog.peers;
-    const int nv = prog.nvalues();
-    std::vector<char> live(nv, 0);
-    for (int k = 0; k < nouts; ++k) live[out_value[k]] = 1;
-    for (int st = prog.nsteps - 1; st >= 0; --st)
-        if (live[P + st]) live[prog.step[st].a] = live[prog.step[st].b] = 1;
-    std::vector<int> last_use(nv, -1);
-    for (int st = 0; st < prog.nsteps; ++st) {
-        if (!live[P + st]) continue;
-        last_use[prog.step[st].a] = st;
-        last_use[prog.step[st].b] = st;
-    }
-    for (int k = 0; k < nouts; ++k) last_use[out_value[k]] = prog.nsteps;  // outputs live to the end
-    // host-side slot assignment
-    std::vector<int> slot(nv, -1), free_slots;
-    int nslots = 0;
-    for (int st = 0; st < prog.nsteps; ++st) {
-        if (!live[P + st]) continue;
-        int d;
-        if (!free_slots.empty()) {
-            d = free_slots.back();
-            free_slots.pop_back();
-        } else {
-            d = nslots++;
-        }
-        slot[P + st] = d;
-        const int a = prog.step[st].a, b = prog.step[st].b;
-        if (a >= P && last_use[a] == st) free_slots.push_back(slot[a]);
-        if (b >= P && b != a && last_use[b] == st) free_slots.push_back(slot[b]);
-    }
-    const size_t stride = arena_stride(n, esz);
-    std::lock_guard<std::mutex> lk(g_mu);
-    FMI_RC_TRY(arena_acquire(stride * static_cast<size_t>(nslots), s));
-    auto addr = [&](int v) -> const void* {
-        return v < P ? ins[v] : static_cast<const char*>(g_state.arena) + stride * static_cast<size_t>(slot[v]);
-    };
+    const sched::StepwisePlan plan = sched::plan_stepwise(prog, out_value, nouts);
+    Scratch::Lease temps(g_arena, arena_stride(n, esz), plan.nslots, s);
+    FMI_RC_TRY(temps.status());
+    auto addr = [&](int v) -> const void* { return v < P ? ins[v] : temps.slot(plan.slot[v]); };
     int rc = FMI_OK;
     for (int st = 0; st < prog.nsteps && rc == FMI_OK; ++st)
-        if (live[P + st])
+        if (plan.live[P + st])
             rc = launch_combine(op, dtype, const_cast<void*>(addr(P + st)), addr(prog.step[st].a), addr(prog.step[st].b), n, s);
     for (int k = 0; k < nouts && rc == FMI_OK; ++k) {
         const void* src = addr(out_value[k]);
@@ -369,8 +419,7 @@ int run_program_stepwise(int op, int dtype, const sched::HostProgram& prog, void
             rc = device_copy(outs[k], src, n * esz, s);
         }
     }
-    FMI_HIP_TRY(hipEventRecord(g_state.arena_free, s));
-    return rc;
+    return temps.done(rc);
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -390,16 +439,26 @@ int run_program_stepwise(int op, int dtype, const sched::HostProgram& prog, void
 // instead of 189 for pairwise steps). A dry run only counts the temps.
 // ----------------------------------------------------------------------------------------------------
 struct TreeTemps {
-    bool dry = true;  // dry run: count the temps, launch nothing
-    char* base = nullptr;
-    size_t stride = 0;
+    const Scratch::Lease* lease = nullptr;  // none: a dry run, which counts the temps and launches nothing
     int used = 0;
-    void* next() { return dry ? (++used, nullptr) : base + stride * static_cast<size_t>(used++); }
+    bool dry() const { return !lease; }
+    void* next() { return lease ? lease->slot(used++) : (++used, nullptr); }
 };
+
+// A blocked program's two walks: the dry one counts its temps, the real one runs on an arena lease of that many.
+template <class Walk>
+int with_arena_temps(int dtype, size_t n, hipStream_t s, Walk&& walk) {
+    TreeTemps count;
+    FMI_RC_TRY(walk(count));
+    Scratch::Lease lease(g_arena, arena_stride(n, dtype_size(dtype)), count.used, s);
+    FMI_RC_TRY(lease.status());
+    TreeTemps t{&lease};
+    return lease.done(walk(t));
+}
 
 int tree_blocked(int op, int dtype, int alg, void* out, const void* const* ins, int P, int rank, size_t n,
                  hipStream_t s, TreeTemps& t) {
-    const bool dry = t.dry;
+    const bool dry = t.dry();
     constexpr int B16 = sched::kMaxFusedPeers;
     if (P == 1) {
         if (!dry && out != ins[0]) FMI_RC_TRY(device_copy(out, ins[0], n * dtype_size(dtype), s));
@@ -407,10 +466,7 @@ int tree_blocked(int op, int dtype, int alg, void* out, const void* const* ins, 
     }
     if (P <= sched::max_fused_peers(alg)) {
         if (dry) return FMI_OK;
-        PeerPtrs ptrs{};
-        for (int p = 0; p < P; ++p) ptrs.in[p] = ins[p];
-        ptrs.out[0] = out;
-        return launch_fused(alg, op, dtype, P, ptrs, n, rank, s);
+        return launch_fused(alg, op, dtype, P, peer_table<PeerPtrs>(ins, P, out), n, rank, s);
     }
     switch (alg) {
         case FMI_ALG_REDUCE_LTR: {
@@ -419,11 +475,8 @@ int tree_blocked(int op, int dtype, int alg, void* out, const void* const* ins, 
             for (int p = B16; p < P; p += B16 - 1) {
                 const int m = std::min(B16 - 1, P - p);
                 if (dry) continue;
-                PeerPtrs ptrs{};
-                ptrs.in[0] = acc;
-                for (int j = 0; j < m; ++j) ptrs.in[1 + j] = ins[p + j];
-                ptrs.out[0] = p + m == P ? out : acc;  // elementwise: reading and writing acc in one pass is safe
-                FMI_RC_TRY(launch_fused(sched::kReduceLtr, op, dtype, 1 + m, ptrs, n, 0, s));
+                void* to = p + m == P ? out : acc;  // elementwise: reading and writing acc in one pass is safe
+                FMI_RC_TRY(launch_fused(sched::kReduceLtr, op, dtype, 1 + m, peer_table<PeerPtrs>(ins + p, m, to, acc), n, 0, s));
             }
             return FMI_OK;
         }
@@ -457,12 +510,9 @@ int tree_blocked(int op, int dtype, int alg, void* out, const void* const* ins, 
                 y.insert(y.end(), ins + pow2 + lo, ins + pow2 + lo + m);
                 void* v = t.next();
                 if (m == B16) {
-                    if (!dry) {
-                        PeerPtrs ptrs{};
-                        for (int j = 0; j < 2 * B16; ++j) ptrs.in[j] = y[j];
-                        ptrs.out[0] = v;
-                        FMI_RC_TRY(launch_fused(sched::kAllreducePrefold16, op, dtype, 2 * B16, ptrs, n, r % B16, s));
-                    }
+                    if (!dry)
+                        FMI_RC_TRY(launch_fused(sched::kAllreducePrefold16, op, dtype, 2 * B16,
+                                                peer_table<PeerPtrs>(y.data(), 2 * B16, v), n, r % B16, s));
                 } else {
                     FMI_RC_TRY(tree_blocked(op, dtype, alg, v, y.data(), static_cast<int>(y.size()), r % B16, n, s, t));
                 }
@@ -496,16 +546,12 @@ constexpr int kSuperPeers = kMaxOnePassScanBlocks * sched::kScanBlock;  // 128
 int chain_superblocks(int op, int dtype, bool scan, void* const* outs, void* out, const void* const* ins, int P,
                       size_t n, hipStream_t s) {
     for (int k = 0; k < P;) {
-        BlockedScanPtrs ptrs{};
         const bool carry = k > 0;
         const int first = carry ? 1 : 0;
         const int m = std::min(kSuperPeers - first, P - k);
-        if (carry) ptrs.in[0] = scan ? outs[k - 1] : out;
-        for (int j = 0; j < m; ++j) {
-            ptrs.in[first + j] = ins[k + j];
-            if (scan) ptrs.out[first + j] = outs[k + j];
-        }
-        if (!scan) ptrs.out[0] = out;
+        const void* from = !carry ? nullptr : scan ? outs[k - 1] : out;
+        const BlockedScanPtrs ptrs = scan ? peer_table<BlockedScanPtrs>(ins + k, outs + k, m, from)
+                                          : peer_table<BlockedScanPtrs>(ins + k, m, out, from);
         FMI_RC_TRY(launch_chain_one_pass(op, dtype, scan, m + first, ptrs, n, s, carry));
         k += m;
     }
@@ -518,16 +564,8 @@ int reduce_level(int op, int dtype, void* out, const void* const* vals, int P, s
         if (out != vals[0]) FMI_RC_TRY(device_copy(out, vals[0], n * dtype_size(dtype), s));
         return FMI_OK;
     }
-    if (P <= sched::kMaxFusedPeers) {
-        PeerPtrs ptrs{};
-        for (int p = 0; p < P; ++p) ptrs.in[p] = vals[p];
-        ptrs.out[0] = out;
-        return launch_fused(sched::kReduce, op, dtype, P, ptrs, n, 0, s);
-    }
-    BlockedScanPtrs ptrs{};
-    for (int p = 0; p < P; ++p) ptrs.in[p] = vals[p];
-    ptrs.out[0] = out;
-    return launch_tree_blocks_one_pass(op, dtype, FMI_ALG_REDUCE, P, ptrs, n, 0, s);
+    if (P <= sched::kMaxFusedPeers) return launch_fused(sched::kReduce, op, dtype, P, peer_table<PeerPtrs>(vals, P, out), n, 0, s);
+    return launch_tree_blocks_one_pass(op, dtype, FMI_ALG_REDUCE, P, peer_table<BlockedScanPtrs>(vals, P, out), n, 0, s);
 }
 
 bool tree_superblocks_cover(int op, int dtype, int alg, int P) {
@@ -542,10 +580,8 @@ bool tree_superblocks_cover(int op, int dtype, int alg, int P) {
 // reduce_no_order over P > 128 peers (transformed ids, root 0) as superblocks of 128.
 int reduce_superblocks(int op, int dtype, void* out, const void* const* ins, int P, size_t n, hipStream_t s) {
     const int S = (P + kSuperPeers - 1) / kSuperPeers;
-    std::lock_guard<std::mutex> lk(g_mu);
-    const size_t stride = arena_stride(n, dtype_size(dtype));
-    FMI_RC_TRY(arena_acquire(stride * static_cast<size_t>(S), s));
-    char* base = static_cast<char*>(g_state.arena);
+    Scratch::Lease temps(g_arena, arena_stride(n, dtype_size(dtype)), S, s);
+    FMI_RC_TRY(temps.status());
     std::vector<const void*> vals(S);
     int rc = FMI_OK;
     for (int b = 0; b < S && rc == FMI_OK; ++b) {
@@ -555,13 +591,12 @@ int reduce_superblocks(int op, int dtype, void* out, const void* const* ins, int
             vals[b] = ins[lo];
             continue;
         }
-        void* v = base + stride * static_cast<size_t>(b);
+        void* v = temps.slot(b);
         rc = reduce_level(op, dtype, v, ins + lo, m, n, s);
         vals[b] = v;
     }
     if (rc == FMI_OK) rc = reduce_level(op, dtype, out, vals.data(), S, n, s);
-    FMI_HIP_TRY(hipEventRecord(g_state.arena_free, s));
-    return rc;
+    return temps.done(rc);
 }
 
 // allreduce_no_order over P = 2^k >= 128 peers as superblocks of 64 peers (profiles/archive/r02_ab_allreduce_superblocks64.jsonl, 1 GiB of
@@ -582,35 +617,25 @@ bool allreduce_superblocks_cover(int op, int dtype, int P) {
 int allreduce_superblocks(int op, int dtype, void* out, const void* const* ins, int P, int rank, size_t n,
                           hipStream_t s) {
     const int S = P / kAllreduceSuper;
-    std::lock_guard<std::mutex> lk(g_mu);
-    const size_t stride = arena_stride(n, dtype_size(dtype));
-    FMI_RC_TRY(arena_acquire(stride * static_cast<size_t>(S), s));
-    char* base = static_cast<char*>(g_state.arena);
+    Scratch::Lease temps(g_arena, arena_stride(n, dtype_size(dtype)), S, s);
+    FMI_RC_TRY(temps.status());
     std::vector<const void*> vals(S);
     int rc = FMI_OK;
     for (int b = 0; b < S && rc == FMI_OK; ++b) {
-        BlockedScanPtrs ptrs{};
-        for (int p = 0; p < kAllreduceSuper; ++p) ptrs.in[p] = ins[b * kAllreduceSuper + p];
-        void* v = base + stride * static_cast<size_t>(b);
-        ptrs.out[0] = v;
-        rc = launch_tree_blocks_one_pass(op, dtype, FMI_ALG_ALLREDUCE, kAllreduceSuper, ptrs, n, rank % kAllreduceSuper, s);
+        void* v = temps.slot(b);
+        rc = launch_tree_blocks_one_pass(op, dtype, FMI_ALG_ALLREDUCE, kAllreduceSuper,
+                                         peer_table<BlockedScanPtrs>(ins + b * kAllreduceSuper, kAllreduceSuper, v), n,
+                                         rank % kAllreduceSuper, s);
         vals[b] = v;
     }
     if (rc == FMI_OK) {
-        if (S <= sched::kMaxFusedPeers) {
-            PeerPtrs ptrs{};
-            for (int b = 0; b < S; ++b) ptrs.in[b] = vals[b];
-            ptrs.out[0] = out;
-            rc = launch_fused(sched::kAllreduce, op, dtype, S, ptrs, n, rank / kAllreduceSuper, s);
-        } else {
-            BlockedScanPtrs ptrs{};
-            for (int b = 0; b < S; ++b) ptrs.in[b] = vals[b];
-            ptrs.out[0] = out;
-            rc = launch_tree_blocks_one_pass(op, dtype, FMI_ALG_ALLREDUCE, S, ptrs, n, rank / kAllreduceSuper, s);
-        }
+        if (S <= sched::kMaxFusedPeers)
+            rc = launch_fused(sched::kAllreduce, op, dtype, S, peer_table<PeerPtrs>(vals.data(), S, out), n, rank / kAllreduceSuper, s);
+        else
+            rc = launch_tree_blocks_one_pass(op, dtype, FMI_ALG_ALLREDUCE, S, peer_table<BlockedScanPtrs>(vals.data(), S, out), n,
+                                             rank / kAllreduceSuper, s);
     }
-    FMI_HIP_TRY(hipEventRecord(g_state.arena_free, s));
-    return rc;
+    return temps.done(rc);
 }
 
 int run_tree_blocked(int op, int dtype, int alg, void* out, const void* const* ins, int P, int rank, size_t n,
@@ -623,10 +648,7 @@ int run_tree_blocked(int op, int dtype, int alg, void* out, const void* const* i
             return allreduce_superblocks(op, dtype, out, ins, P, rank, n, s);
     }
     if (g_tune[FMI_TUNE_BLOCKS_ONE_PASS].load() != 0 && alg == FMI_ALG_REDUCE_LTR && P <= kMaxOnePassScanBlocks * 16) {
-        BlockedScanPtrs ptrs{};
-        for (int p = 0; p < P; ++p) ptrs.in[p] = ins[p];
-        ptrs.out[0] = out;
-        return launch_chain_one_pass(op, dtype, false, P, ptrs, n, s);
+        return launch_chain_one_pass(op, dtype, false, P, peer_table<BlockedScanPtrs>(ins, P, out), n, s);
     }
     if (g_tune[FMI_TUNE_BLOCKS_ONE_PASS].load() != 0 && prefold_blocks_one_pass_covers(alg, P)) {
         const int pow2 = 1 << sched::floor_log2(P);
@@ -639,22 +661,10 @@ int run_tree_blocked(int op, int dtype, int alg, void* out, const void* const* i
         return launch_prefold_blocks_one_pass(op, dtype, P, ptrs, n, r >> 4, s);
     }
     if (g_tune[FMI_TUNE_BLOCKS_ONE_PASS].load() != 0 && tree_blocks_one_pass_covers(op, dtype, alg, P)) {
-        BlockedScanPtrs ptrs{};
-        for (int p = 0; p < P; ++p) ptrs.in[p] = ins[p];
-        ptrs.out[0] = out;
-        return launch_tree_blocks_one_pass(op, dtype, alg, P, ptrs, n, alg == FMI_ALG_ALLREDUCE ? rank : 0, s);
+        return launch_tree_blocks_one_pass(op, dtype, alg, P, peer_table<BlockedScanPtrs>(ins, P, out), n,
+                                           alg == FMI_ALG_ALLREDUCE ? rank : 0, s);
     }
-    TreeTemps count;
-    FMI_RC_TRY(tree_blocked(op, dtype, alg, out, ins, P, rank, n, s, count));
-    std::lock_guard<std::mutex> lk(g_mu);
-    TreeTemps t;
-    t.dry = false;
-    t.stride = arena_stride(n, dtype_size(dtype));
-    FMI_RC_TRY(arena_acquire(t.stride * static_cast<size_t>(count.used), s));
-    t.base = static_cast<char*>(g_state.arena);
-    const int rc = tree_blocked(op, dtype, alg, out, ins, P, rank, n, s, t);
-    FMI_HIP_TRY(hipEventRecord(g_state.arena_free, s));
-    return rc;
+    return with_arena_temps(dtype, n, s, [&](TreeTemps& t) { return tree_blocked(op, dtype, alg, out, ins, P, rank, n, s, t); });
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -671,29 +681,19 @@ int run_tree_blocked(int op, int dtype, int alg, void* out, const void* const* i
 int scan_blocked(int op, int dtype, int alg, void* const* outs, const void* const* ins, int P, size_t n,
                  hipStream_t s, TreeTemps& t) {
     constexpr int BL = sched::kScanBlock;
-    const bool dry = t.dry;
+    const bool dry = t.dry();
     if (P == 1) {
         if (!dry && outs[0] != ins[0]) FMI_RC_TRY(device_copy(outs[0], ins[0], n * dtype_size(dtype), s));
         return FMI_OK;
     }
     if (P <= sched::max_fused_peers(alg)) {
         if (dry) return FMI_OK;
-        PeerPtrs ptrs{};
-        for (int p = 0; p < P; ++p) {
-            ptrs.in[p] = ins[p];
-            ptrs.out[p] = outs[p];
-        }
-        return launch_fused(alg, op, dtype, P, ptrs, n, 0, s);
+        return launch_fused(alg, op, dtype, P, peer_table<PeerPtrs>(ins, outs, P), n, 0, s);
     }
     auto carry_block = [&](int lo, int m, const void* carry) -> int {
         if (dry) return FMI_OK;
-        PeerPtrs ptrs{};
-        ptrs.in[0] = carry;
-        for (int j = 0; j < m; ++j) {
-            ptrs.in[1 + j] = ins[lo + j];
-            ptrs.out[1 + j] = outs[lo + j];
-        }
-        return launch_fused(alg == FMI_ALG_SCAN ? sched::kScanCarry : sched::kScanLtrCarry, op, dtype, m + 1, ptrs, n, 0, s);
+        return launch_fused(alg == FMI_ALG_SCAN ? sched::kScanCarry : sched::kScanLtrCarry, op, dtype, m + 1,
+                            peer_table<PeerPtrs>(ins + lo, outs + lo, m, carry), n, 0, s);
     };
     if (alg == FMI_ALG_SCAN_LTR) {
         FMI_RC_TRY(scan_blocked(op, dtype, alg, outs, ins, BL, n, s, t));
@@ -731,42 +731,17 @@ int run_scan_blocked(int op, int dtype, int alg, void* const* outs, const void* 
     if (alg == FMI_ALG_SCAN_LTR && P > kSuperPeers && g_tune[FMI_TUNE_BLOCKS_ONE_PASS].load() != 0)
         return chain_superblocks(op, dtype, true, outs, nullptr, ins, P, n, s);
     if (alg == FMI_ALG_SCAN_LTR && P <= kMaxOnePassScanBlocks * BL && g_tune[FMI_TUNE_BLOCKS_ONE_PASS].load() != 0) {
-        BlockedScanPtrs ptrs{};
-        for (int p = 0; p < P; ++p) {
-            ptrs.in[p] = ins[p];
-            ptrs.out[p] = outs[p];
-        }
-        return launch_chain_one_pass(op, dtype, true, P, ptrs, n, s);
+        return launch_chain_one_pass(op, dtype, true, P, peer_table<BlockedScanPtrs>(ins, outs, P), n, s);
     }
     if (alg == FMI_ALG_SCAN && B >= 2 && B <= kMaxOnePassScanBlocks && g_tune[FMI_TUNE_BLOCKS_ONE_PASS].load() != 0) {
         // every full block in one pass (fmi_fused_scan_blocked.hip), then a ragged block as scan_blocked's
         // carry program from S_{B-1} = outs[16 B - 1]
-        BlockedScanPtrs ptrs{};
-        for (int p = 0; p < B * BL; ++p) {
-            ptrs.in[p] = ins[p];
-            ptrs.out[p] = outs[p];
-        }
-        FMI_RC_TRY(launch_scan_blocks_one_pass(op, dtype, B, ptrs, n, s));
+        FMI_RC_TRY(launch_scan_blocks_one_pass(op, dtype, B, peer_table<BlockedScanPtrs>(ins, outs, B * BL), n, s));
         if (r == 0) return FMI_OK;
-        PeerPtrs c{};
-        c.in[0] = outs[B * BL - 1];
-        for (int j = 0; j < r; ++j) {
-            c.in[1 + j] = ins[B * BL + j];
-            c.out[1 + j] = outs[B * BL + j];
-        }
-        return launch_fused(sched::kScanCarry, op, dtype, r + 1, c, n, 0, s);
+        return launch_fused(sched::kScanCarry, op, dtype, r + 1, peer_table<PeerPtrs>(ins + B * BL, outs + B * BL, r, outs[B * BL - 1]), n,
+                            0, s);
     }
-    TreeTemps count;
-    FMI_RC_TRY(scan_blocked(op, dtype, alg, outs, ins, P, n, s, count));
-    std::lock_guard<std::mutex> lk(g_mu);
-    TreeTemps t;
-    t.dry = false;
-    t.stride = arena_stride(n, dtype_size(dtype));
-    FMI_RC_TRY(arena_acquire(t.stride * static_cast<size_t>(count.used), s));
-    t.base = static_cast<char*>(g_state.arena);
-    const int rc = scan_blocked(op, dtype, alg, outs, ins, P, n, s, t);
-    FMI_HIP_TRY(hipEventRecord(g_state.arena_free, s));
-    return rc;
+    return with_arena_temps(dtype, n, s, [&](TreeTemps& t) { return scan_blocked(op, dtype, alg, outs, ins, P, n, s, t); });
 }
 
 int check_peer_count(int P) {
@@ -780,6 +755,30 @@ int check_peer_args(int op, int dtype, int P) {
     if (int rc = refuse_fp4(dtype)) return rc;
     if (dtype_size(dtype) == 0) return fail(FMI_ERR_INVALID, "unknown dtype " + std::to_string(dtype));
     return check_peer_count(P);
+}
+
+// What the tree entry points check after P, in this order: rank / root, the arrays themselves (`arrays`: every array
+// argument the call needs is non-null), then every peer's bucket and, for the MX calls, its scale array.
+int check_tree_buffers(int P, int rank, bool arrays, const void* const* ins, const void* const* in_scales = nullptr) {
+    if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
+    if (!arrays) return fail(FMI_ERR_INVALID, "null buffer");
+    for (int p = 0; p < P; ++p)
+        if (!ins[p] || (in_scales && !in_scales[p]))
+            return fail(FMI_ERR_INVALID, in_scales ? "null input bucket or scale array" : "null input bucket");
+    return FMI_OK;
+}
+
+// The alg and out_dtype checks of the scaled and MX calls; `what`: "a scaled reduction" / "an MX reduction".
+int check_alg_out_dtype(const std::string& w, const char* what, int alg, int out_dtype, int dtype) {
+    if (alg == FMI_ALG_SCAN || alg == FMI_ALG_SCAN_LTR)
+        return fail(FMI_ERR_INVALID, w + "alg " + std::to_string(alg) + " is a scan algorithm; " + what + " takes "
+                                         "FMI_ALG_ALLREDUCE, FMI_ALG_REDUCE or FMI_ALG_REDUCE_LTR");
+    if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
+        return fail(FMI_ERR_INVALID, w + "unknown alg " + std::to_string(alg));
+    if (out_dtype != dtype && out_dtype != FMI_F32)
+        return fail(FMI_ERR_INVALID, w + "out_dtype " + std::to_string(out_dtype) + " must be the input dtype (" +
+                                         std::to_string(dtype) + ") or FMI_F32");
+    return FMI_OK;
 }
 
 // Symbolic evaluation of a program, for fmi_schedule_expr.
@@ -807,77 +806,44 @@ std::string expr_of(const sched::HostProgram& prog, int v) {
 }
 
 // ----------------------------------------------------------------------------------------------------
-// FMI_ACC_F32 beyond the fused acc32 kernels (P > 16, or a bucket that is not 16-B aligned): widen every input into
-// an f32 temporary, run the library's own FMI_F32 program on the temporaries (every family f32 has, unchanged), narrow
-// every stored output: out = narrow(F32_program(widen(x))) by construction. The inner program may take the scratch
-// arena under g_mu and reallocate it, so the temporaries live in an allocation of their own (g_acc, ordered by its
-// own event the way arena_acquire orders the arena, and like it not capturable) under a lock of their own: g_acc_mu
-// is held while the call's launches are enqueued, g_mu is only ever taken inside it, never around it.
+// The f32 bridge: what a call runs when its values are f32 and no fused kernel serves it (FMI_ACC_F32 at P > 16 or on
+// a bucket that is not 16-B aligned, the scaled and MX calls beyond their fused kernels). Every input is widened into
+// an f32 temporary, the library's own FMI_F32 program runs on the temporaries (every family f32 has, unchanged), and
+// a finishing launch stores each output: out = finish(F32_program(widen(x))) by construction. The inner program may
+// take the scratch arena and reallocate it, so the temporaries are a Scratch of their own (g_f32_temps, whose lease
+// is held while the call's launches are enqueued; the lock order is stated at the type).
+//   widen(p, t)      launches input p's conversion into temporary t;
+//   inner(fo, fi)    runs the FMI_F32 program on the temporaries fi[0..P) into fo[0..nouts), where fo[k] is temporary
+//                    out_slot[k] (an input's own temporary where the program may run in place, a further one
+//                    otherwise; out_slot == nullptr: temporary k); it may launch nothing, or store elsewhere;
+//   finish(k, t)     stores output k from temporary t = fo[k]; it may launch nothing.
+// `ntemps` temporaries in all.
 // ----------------------------------------------------------------------------------------------------
-struct AccTemps {
-    void* buf = nullptr;
-    size_t bytes = 0;
-    hipEvent_t free = nullptr;  // the work that last used buf has drained
-};
-std::mutex g_acc_mu;
-AccTemps g_acc;
-
-int acc_acquire(size_t need, hipStream_t s) {  // caller holds g_acc_mu
-    FMI_RC_TRY(refuse_capture(s, "f32 temporaries (FMI_ACC_F32 beyond 16 peers or on unaligned buckets)"));
-    if (!g_acc.free) FMI_HIP_TRY(hipEventCreateWithFlags(&g_acc.free, hipEventDisableTiming));
-    if (g_acc.bytes < need) {
-        FMI_HIP_TRY(hipEventSynchronize(g_acc.free));  // previous users have drained
-        if (g_acc.buf) FMI_HIP_TRY(hipFree(g_acc.buf));
-        g_acc.buf = nullptr;
-        g_acc.bytes = 0;
-        const hipError_t e = hipMalloc(&g_acc.buf, need);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();  // not left for the next launch's error check to find
-            return fail(FMI_ERR_ALLOC, "hipMalloc(" + std::to_string(need) + ") for FMI_ACC_F32's f32 temporaries: " +
-                                           hipGetErrorString(e));
-        }
-        g_acc.bytes = need;
-    }
-    FMI_HIP_TRY(hipStreamWaitEvent(s, g_acc.free, 0));
-    return FMI_OK;
-}
-
-void acc_release() {  // fmi_dev_finalize (holding g_acc_mu), after the device has drained
-    if (g_acc.buf) (void)hipFree(g_acc.buf);
-    if (g_acc.free) (void)hipEventDestroy(g_acc.free);
-    g_acc = AccTemps{};
-}
-
-// `inner(f32_outs, f32_ins)` runs the FMI_F32 program; f32 output k is temporary `out_slot[k]` (an input's own
-// temporary where the program may run in place, a further one otherwise), `ntemps` temporaries in all.
-template <class Inner>
-int acc32_fallback(int dtype, void* const* outs, const int* out_slot, int nouts, const void* const* ins, int P,
-                   int ntemps, size_t n, hipStream_t s, Inner&& inner) {
-    const size_t stride = arena_stride(n, sizeof(float));
-    size_t need = 0;
-    if (__builtin_mul_overflow(stride, static_cast<size_t>(ntemps), &need))
-        return fail(FMI_ERR_ALLOC, "FMI_ACC_F32's f32 temporaries: size overflows");
-    std::lock_guard<std::mutex> lk(g_acc_mu);
-    FMI_RC_TRY(acc_acquire(need, s));
-    auto temp = [&](int k) { return reinterpret_cast<float*>(static_cast<char*>(g_acc.buf) + stride * static_cast<size_t>(k)); };
+template <class Widen, class Inner, class Finish>
+int f32_bridge(int ntemps, const int* out_slot, int nouts, int P, size_t n, hipStream_t s, Widen&& widen, Inner&& inner,
+               Finish&& finish) {
+    Scratch::Lease temps(g_f32_temps, arena_stride(n, sizeof(float)), ntemps, s);
+    FMI_RC_TRY(temps.status());
     std::vector<const void*> fin(P);
     std::vector<void*> fout(nouts);
     int rc = FMI_OK;
     for (int p = 0; p < P && rc == FMI_OK; ++p) {
-        fin[p] = temp(p);
-        rc = launch_widen_f32(dtype, temp(p), ins[p], n, s);
+        fin[p] = temps.slot(p);
+        rc = widen(p, static_cast<float*>(temps.slot(p)));
     }
-    for (int k = 0; k < nouts; ++k) fout[k] = temp(out_slot[k]);
+    for (int k = 0; k < nouts; ++k) fout[k] = temps.slot(out_slot ? out_slot[k] : k);
     if (rc == FMI_OK) rc = inner(fout.data(), fin.data());
-    for (int k = 0; k < nouts && rc == FMI_OK; ++k) rc = launch_narrow_f32(dtype, outs[k], temp(out_slot[k]), n, s);
-    FMI_HIP_TRY(hipEventRecord(g_acc.free, s));
-    return rc;
+    for (int k = 0; k < nouts && rc == FMI_OK; ++k) rc = finish(k, static_cast<const float*>(fout[k]));
+    return temps.done(rc);
 }
 
-bool all_aligned16(const void* const* a, void* const* b, int P) {
-    bool ok = true;
-    for (int p = 0; p < P; ++p) ok = ok && aligned16(a[p]) && (!b || aligned16(b[p]));
-    return ok;
+// FMI_ACC_F32's bridge: out = narrow(F32_program(widen(x))), every stored output narrowed to the storage dtype.
+template <class Inner>
+int acc32_fallback(int dtype, void* const* outs, const int* out_slot, int nouts, const void* const* ins, int P,
+                   int ntemps, size_t n, hipStream_t s, Inner&& inner) {
+    return f32_bridge(
+        ntemps, out_slot, nouts, P, n, s, [&](int p, float* t) { return launch_widen_f32(dtype, t, ins[p], n, s); }, inner,
+        [&](int k, const float* t) { return launch_narrow_f32(dtype, outs[k], t, n, s); });
 }
 
 }  // namespace
@@ -889,30 +855,15 @@ int reduce_partials(int op, int dtype_arg, void* const* outs, const void* const*
     FMI_RC_TRY(canonical_dtype(op, dtype_arg, true, P, &dtype));
     if (accumulates_f32(dtype)) {
         const int st = storage_dtype(dtype);
-        if (P <= sched::kMaxFusedPeers && all_aligned16(ins, outs, P)) {
-            PeerPtrs ptrs{};
-            for (int p = 0; p < P; ++p) {
-                ptrs.in[p] = ins[p];
-                ptrs.out[p] = outs[p];
-            }
-            return launch_fused(sched::kReducePartials, op, dtype, P, ptrs, n, 0, s);
-        }
-        std::vector<int> slot(P);
-        for (int p = 0; p < P; ++p) slot[p] = p;  // in place: partial t overwrites input t's temporary
-        return acc32_fallback(st, outs, slot.data(), P, ins, P, P, n, s, [&](void* const* fo, const void* const* fi) {
+        if (P <= sched::kMaxFusedPeers && all_aligned16(ins, outs, P))
+            return launch_fused(sched::kReducePartials, op, dtype, P, peer_table<PeerPtrs>(ins, outs, P), n, 0, s);
+        // in place (no out_slot): partial t overwrites input t's temporary
+        return acc32_fallback(st, outs, nullptr, P, ins, P, P, n, s, [&](void* const* fo, const void* const* fi) {
             return reduce_partials(op, FMI_F32, fo, fi, P, n, s);
         });
     }
-    bool aligned = true;
-    for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]) && aligned16(outs[p]);
-    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned && fused_covers(op, dtype, sched::kReducePartials, P)) {
-        PeerPtrs ptrs{};
-        for (int p = 0; p < P; ++p) {
-            ptrs.in[p] = ins[p];
-            ptrs.out[p] = outs[p];
-        }
-        return launch_fused(sched::kReducePartials, op, dtype, P, ptrs, n, 0, s);
-    }
+    if (P >= 2 && P <= sched::kMaxFusedPeers && all_aligned16(ins, outs, P) && fused_covers(op, dtype, sched::kReducePartials, P))
+        return launch_fused(sched::kReducePartials, op, dtype, P, peer_table<PeerPtrs>(ins, outs, P), n, 0, s);
     const sched::HostProgram prog = sched::build_host(sched::kReducePartials, P);
     if (!prog.ok) return fail(FMI_ERR_INVALID, "schedule construction failed");
     std::vector<int> values(prog.out.begin(), prog.out.end());
@@ -1026,7 +977,9 @@ int fmi_dev_init(int device) {
 }
 
 int fmi_dev_finalize(void) {
-    std::lock_guard<std::mutex> acc_lk(g_acc_mu);  // before g_mu: the order an FMI_ACC_F32 fallback call takes them in
+    // No lease is outstanding while both are held, in the Scratch order; g_mu after them (no lease holder takes it).
+    std::lock_guard<std::mutex> f32_lk(g_f32_temps.mu);
+    std::lock_guard<std::mutex> arena_lk(g_arena.mu);
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_state.device < 0) return FMI_OK;
     (void)hipSetDevice(g_state.device);
@@ -1040,9 +993,8 @@ int fmi_dev_finalize(void) {
         pipes().all.clear();
         pipes().idle.clear();
     }
-    acc_release();
-    if (g_state.arena) (void)hipFree(g_state.arena);
-    if (g_state.arena_free) (void)hipEventDestroy(g_state.arena_free);
+    g_f32_temps.release();
+    g_arena.release();
     if (g_state.stream) (void)hipStreamDestroy(g_state.stream);
     g_state = DeviceState{};
     return FMI_OK;
@@ -1450,10 +1402,7 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
     if (int rc = check_peer_args(op, dtype, P)) return rc;
     if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
         return fail(FMI_ERR_INVALID, "fmi_dev_reduce_tree: alg must be ALLREDUCE, REDUCE or REDUCE_LTR");
-    if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
-    if (!out || !ins) return fail(FMI_ERR_INVALID, "null buffer");
-    for (int p = 0; p < P; ++p)
-        if (!ins[p]) return fail(FMI_ERR_INVALID, "null input bucket");
+    if (int rc = check_tree_buffers(P, rank, out && ins, ins)) return rc;
     if (int rc = require_device()) return rc;
     if (n == 0) return FMI_OK;
     hipStream_t s = resolve(stream);
@@ -1461,8 +1410,7 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
     // input slot t takes real peer (t + root) % P.
     std::vector<const void*> order(P);
     for (int t = 0; t < P; ++t) order[t] = ins[alg == FMI_ALG_REDUCE ? (t + rank) % P : t];
-    bool aligned = aligned16(out);
-    for (int p = 0; p < P; ++p) aligned = aligned && aligned16(order[p]);
+    const bool aligned = aligned16(out) && all_aligned16(order.data(), nullptr, P);
     if (acc && (P > sched::kMaxFusedPeers || !aligned)) {
         // the inner call applies the root's rotation itself: the temporaries keep the caller's order
         const int slot = P;  // the result in a temporary of its own
@@ -1480,10 +1428,7 @@ static int reduce_tree_impl(int op, int dtype_arg, int alg, void* out, const voi
     const int fused_op = avg ? FMI_OP_AVG : op;  // a mean left by now has a fused kernel: 2 <= P <= 16, aligned
     if (P >= 2 && aligned && fused_covers(fused_op, canon, alg, P)) {
         if (!fused_has_unit(alg, fused_op, canon, P)) return run_tree_blocked(op, dtype, alg, out, order.data(), P, rank, n, s);
-        PeerPtrs ptrs{};
-        for (int p = 0; p < P; ++p) ptrs.in[p] = order[p];
-        ptrs.out[0] = out;
-        return launch_fused(alg, fused_op, canon, P, ptrs, n, rank, s);
+        return launch_fused(alg, fused_op, canon, P, peer_table<PeerPtrs>(order.data(), P, out), n, rank, s);
     }
     const sched::HostProgram prog = sched::build_host(alg, P);
     if (!prog.ok) return fail(FMI_ERR_INVALID, "schedule construction failed");
@@ -1508,23 +1453,16 @@ static int scan_peers_impl(int op, int dtype_arg, int alg, void* const* outs, co
     if (int rc = require_device()) return rc;
     if (n == 0) return FMI_OK;
     hipStream_t s = resolve(stream);
-    bool aligned = true;
-    for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]) && aligned16(outs[p]);
+    const bool aligned = all_aligned16(ins, outs, P);
     if (acc && (P > sched::kMaxFusedPeers || !aligned)) {
-        std::vector<int> slot(P);
-        for (int p = 0; p < P; ++p) slot[p] = p;  // in place: prefix p overwrites input p's temporary
-        return acc32_fallback(dtype, outs, slot.data(), P, ins, P, P, n, s, [&](void* const* fo, const void* const* fi) {
+        // in place (no out_slot): prefix p overwrites input p's temporary
+        return acc32_fallback(dtype, outs, nullptr, P, ins, P, P, n, s, [&](void* const* fo, const void* const* fi) {
             return scan_peers_impl(op, FMI_F32, alg, fo, fi, P, n, stream);
         });
     }
     if (P >= 2 && aligned && fused_covers(op, canon, alg, P)) {
         if (!fused_has_unit(alg, op, canon, P)) return run_scan_blocked(op, dtype, alg, outs, ins, P, n, s);
-        PeerPtrs ptrs{};
-        for (int p = 0; p < P; ++p) {
-            ptrs.in[p] = ins[p];
-            ptrs.out[p] = outs[p];
-        }
-        return launch_fused(alg, op, canon, P, ptrs, n, 0, s);
+        return launch_fused(alg, op, canon, P, peer_table<PeerPtrs>(ins, outs, P), n, 0, s);
     }
     const sched::HostProgram prog = sched::build_host(alg, P);
     if (!prog.ok) return fail(FMI_ERR_INVALID, "schedule construction failed");
@@ -1780,23 +1718,13 @@ int scaled_check_args(const char* who, int op, int dtype_arg, int alg, int out_d
     if (!is_fp8_dtype(*dtype))
         return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype_arg) + " is not FMI_F8E4M3 or FMI_F8E5M2, the storage "
                                          "types a scaled bucket can have");
-    if (alg == FMI_ALG_SCAN || alg == FMI_ALG_SCAN_LTR)
-        return fail(FMI_ERR_INVALID, w + "alg " + std::to_string(alg) + " is a scan algorithm; a scaled reduction takes "
-                                         "FMI_ALG_ALLREDUCE, FMI_ALG_REDUCE or FMI_ALG_REDUCE_LTR");
-    if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
-        return fail(FMI_ERR_INVALID, w + "unknown alg " + std::to_string(alg));
-    if (out_dtype != *dtype && out_dtype != FMI_F32)
-        return fail(FMI_ERR_INVALID, w + "out_dtype " + std::to_string(out_dtype) + " must be the input dtype (" +
-                                         std::to_string(*dtype) + ") or FMI_F32");
-    return FMI_OK;
+    return check_alg_out_dtype(w, "a scaled reduction", alg, out_dtype, *dtype);
 }
 
 int reduce_tree_scaled(int dtype, int alg, int out_dtype, void* out, const void* const* ins, const float* in_scales,
                        const float* out_scale, float* amax, int P, int rank, size_t n, hipStream_t s) {
     if (n == 0) return FMI_OK;
-    bool aligned = aligned16(out);
-    for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]);
-    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned) {
+    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned16(out) && all_aligned16(ins, nullptr, P)) {
         // reduce_no_order's transformed ids, as in fmi_dev_reduce_tree: slot t takes peer (t + root) % P, and the
         // kernel reads that peer's scale (ScaledArgs::rot)
         const int rot = alg == FMI_ALG_REDUCE ? rank : 0;
@@ -1805,26 +1733,16 @@ int reduce_tree_scaled(int dtype, int alg, int out_dtype, void* out, const void*
         ptrs.out[0] = out;
         return launch_fused_scaled(alg, dtype, out_dtype, P, ptrs, ScaledArgs{in_scales, out_scale, amax, rot}, n, s);
     }
-    // Beyond the fused kernels: v_p into f32 temporaries (FMI_ACC_F32's allocation and lock), the library's own FMI_F32
-    // SUM program on them (it applies the root's rotation itself) into a temporary of its own, the finishing kernel.
-    const size_t stride = arena_stride(n, sizeof(float));
-    size_t need = 0;
-    if (__builtin_mul_overflow(stride, static_cast<size_t>(P) + 1, &need))
-        return fail(FMI_ERR_ALLOC, "fmi_dev_reduce_tree_scaled's f32 temporaries: size overflows");
-    std::lock_guard<std::mutex> lk(g_acc_mu);
-    FMI_RC_TRY(acc_acquire(need, s));
-    auto temp = [&](int k) { return reinterpret_cast<float*>(static_cast<char*>(g_acc.buf) + stride * static_cast<size_t>(k)); };
-    std::vector<const void*> fin(P);
-    int rc = FMI_OK;
-    for (int p = 0; p < P && rc == FMI_OK; ++p) {
-        fin[p] = temp(p);
-        rc = launch_widen_scale_f32(dtype, temp(p), ins[p], in_scales + p, n, s);
-    }
+    // Beyond the fused kernels, the f32 bridge: v_p into the f32 temporaries, the library's own FMI_F32 SUM program on
+    // them (it applies the root's rotation itself) into a temporary of its own, the finishing kernel.
     // P = 1: S is v_0 itself (the f32 program would copy it)
-    if (rc == FMI_OK && P > 1) rc = reduce_tree_impl(FMI_OP_SUM, FMI_F32, alg, temp(P), fin.data(), P, rank, n, s);
-    if (rc == FMI_OK) rc = launch_scaled_finish(dtype, out_dtype, out, temp(P > 1 ? P : 0), out_scale, amax, n, s);
-    FMI_HIP_TRY(hipEventRecord(g_acc.free, s));
-    return rc;
+    const int S = P > 1 ? P : 0;
+    return f32_bridge(
+        P + 1, &S, 1, P, n, s, [&](int p, float* t) { return launch_widen_scale_f32(dtype, t, ins[p], in_scales + p, n, s); },
+        [&](void* const* fo, const void* const* fi) {
+            return P > 1 ? reduce_tree_impl(FMI_OP_SUM, FMI_F32, alg, fo[0], fi, P, rank, n, s) : FMI_OK;
+        },
+        [&](int, const float* t) { return launch_scaled_finish(dtype, out_dtype, out, t, out_scale, amax, n, s); });
 }
 
 }  // namespace fmi::dev
@@ -1836,10 +1754,7 @@ int fmi_dev_reduce_tree_scaled(int op, int dtype_arg, int alg, int out_dtype, vo
         int dtype = 0;
         if (int rc = scaled_check_args("fmi_dev_reduce_tree_scaled", op, dtype_arg, alg, out_dtype, &dtype)) return rc;
         if (int rc = check_peer_args(op, dtype, P)) return rc;
-        if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
-        if (!out || !ins || !in_scales) return fail(FMI_ERR_INVALID, "null buffer");
-        for (int p = 0; p < P; ++p)
-            if (!ins[p]) return fail(FMI_ERR_INVALID, "null input bucket");
+        if (int rc = check_tree_buffers(P, rank, out && ins && in_scales, ins)) return rc;
         if (int rc = require_device()) return rc;
         return reduce_tree_scaled(dtype, alg, out_dtype, out, ins, in_scales, out_scale, amax, P, rank, n, resolve(stream));
     });
@@ -1862,14 +1777,7 @@ int mx_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype
     if (!is_mx_dtype(*dtype))
         return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype_arg) + " is not FMI_F8E4M3 or FMI_F8E5M2 (MXFP8) or "
                                          "FMI_F4E2M1 (MXFP4), the element types an MX bucket can have");
-    if (alg == FMI_ALG_SCAN || alg == FMI_ALG_SCAN_LTR)
-        return fail(FMI_ERR_INVALID, w + "alg " + std::to_string(alg) + " is a scan algorithm; an MX reduction takes "
-                                         "FMI_ALG_ALLREDUCE, FMI_ALG_REDUCE or FMI_ALG_REDUCE_LTR");
-    if (alg != FMI_ALG_ALLREDUCE && alg != FMI_ALG_REDUCE && alg != FMI_ALG_REDUCE_LTR)
-        return fail(FMI_ERR_INVALID, w + "unknown alg " + std::to_string(alg));
-    if (out_dtype != *dtype && out_dtype != FMI_F32)
-        return fail(FMI_ERR_INVALID, w + "out_dtype " + std::to_string(out_dtype) + " must be the input dtype (" +
-                                         std::to_string(*dtype) + ") or FMI_F32");
+    if (int rc = check_alg_out_dtype(w, "an MX reduction", alg, out_dtype, *dtype)) return rc;
     if (out_dtype != FMI_F32 && !out_scales)
         return fail(FMI_ERR_INVALID, w + "out_scales is NULL: an output of dtype " + std::to_string(out_dtype) +
                                          " needs its scale bytes (only an FMI_F32 output has none)");
@@ -1904,9 +1812,7 @@ int reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* o
                    const void* const* in_scales, int P, int rank, size_t n, hipStream_t s, const uint64_t* seed, uint64_t first) {
     if (n == 0) return FMI_OK;
     const bool wide = out_dtype == FMI_F32;
-    bool aligned = aligned16(out);
-    for (int p = 0; p < P; ++p) aligned = aligned && aligned16(ins[p]);
-    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned) {
+    if (P >= 2 && P <= sched::kMaxFusedPeers && aligned16(out) && all_aligned16(ins, nullptr, P)) {
         // reduce_no_order's transformed ids, as in fmi_dev_reduce_tree: slot t takes peer (t + root) % P, its element
         // bucket and its scale bytes alike
         const int rot = alg == FMI_ALG_REDUCE ? rank : 0;
@@ -1922,33 +1828,25 @@ int reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* o
         mx.seed = seed, mx.first = first;
         return launch_fused_mx(alg, dtype, out_dtype, P, ptrs, mx, n, s);
     }
-    // Beyond the fused kernels: v_p into f32 temporaries (FMI_ACC_F32's allocation and lock), the library's own FMI_F32
-    // program on them (sum or mean; it applies the root's rotation itself), then the quantize kernel. An f32 output
-    // takes the program's result directly.
-    const size_t stride = arena_stride(n, sizeof(float));
-    size_t need = 0;
-    if (__builtin_mul_overflow(stride, static_cast<size_t>(P) + 1, &need))
-        return fail(FMI_ERR_ALLOC, "fmi_dev_reduce_tree_mx's f32 temporaries: size overflows");
-    std::lock_guard<std::mutex> lk(g_acc_mu);
-    FMI_RC_TRY(acc_acquire(need, s));
-    auto temp = [&](int k) { return reinterpret_cast<float*>(static_cast<char*>(g_acc.buf) + stride * static_cast<size_t>(k)); };
-    std::vector<const void*> fin(P);
-    int rc = FMI_OK;
-    // P = 1: S is v_0 itself (the f32 program would copy it; a mean over one peer multiplies by 1)
-    float* S = P > 1 ? temp(P) : wide ? static_cast<float*>(out) : temp(0);
-    for (int p = 0; p < P && rc == FMI_OK; ++p) {
-        fin[p] = temp(p);
-        rc = launch_mx_dequantize(FMI_F32, P > 1 ? temp(p) : S, dtype, ins[p], static_cast<const uint8_t*>(in_scales[p]), n, s);
-    }
-    if (rc == FMI_OK && P > 1) {
-        if (wide) S = static_cast<float*>(out);
-        rc = reduce_tree_impl(op, FMI_F32, alg, S, fin.data(), P, rank, n, s);
-    }
-    if (rc == FMI_OK && !wide)
-        rc = seed ? launch_mx_quantize_sr(dtype, out, static_cast<uint8_t*>(out_scales), FMI_F32, S, n, seed, first, s)
-                  : launch_mx_quantize(dtype, out, static_cast<uint8_t*>(out_scales), FMI_F32, S, n, s);
-    FMI_HIP_TRY(hipEventRecord(g_acc.free, s));
-    return rc;
+    // Beyond the fused kernels, the f32 bridge: v_p into the f32 temporaries, the library's own FMI_F32 program on them
+    // (sum or mean; it applies the root's rotation itself), then the quantize kernel. An f32 output takes the program's
+    // result directly, and has nothing to finish.
+    // P = 1: S is v_0 itself (the f32 program would copy it; a mean over one peer multiplies by 1), dequantized
+    // straight into an f32 output
+    const int S = P > 1 ? P : 0;
+    return f32_bridge(
+        P + 1, &S, 1, P, n, s,
+        [&](int p, float* t) {
+            return launch_mx_dequantize(FMI_F32, P == 1 && wide ? out : t, dtype, ins[p], static_cast<const uint8_t*>(in_scales[p]), n, s);
+        },
+        [&](void* const* fo, const void* const* fi) {
+            return P > 1 ? reduce_tree_impl(op, FMI_F32, alg, wide ? out : fo[0], fi, P, rank, n, s) : FMI_OK;
+        },
+        [&](int, const float* t) {
+            if (wide) return static_cast<int>(FMI_OK);
+            return seed ? launch_mx_quantize_sr(dtype, out, static_cast<uint8_t*>(out_scales), FMI_F32, t, n, seed, first, s)
+                        : launch_mx_quantize(dtype, out, static_cast<uint8_t*>(out_scales), FMI_F32, t, n, s);
+        });
 }
 
 }  // namespace fmi::dev
@@ -1959,10 +1857,7 @@ int fmi_dev_reduce_tree_mx(int op, int dtype_arg, int alg, int out_dtype, void* 
         int dtype = 0;
         if (int rc = mx_check_args("fmi_dev_reduce_tree_mx", op, dtype_arg, alg, out_dtype, out_scales, &dtype)) return rc;
         if (int rc = check_peer_count(P)) return rc;  // op and dtype: mx_check_args above
-        if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
-        if (!out || !ins || !in_scales) return fail(FMI_ERR_INVALID, "null buffer");
-        for (int p = 0; p < P; ++p)
-            if (!ins[p] || !in_scales[p]) return fail(FMI_ERR_INVALID, "null input bucket or scale array");
+        if (int rc = check_tree_buffers(P, rank, out && ins && in_scales, ins, in_scales)) return rc;
         if (int rc = require_device()) return rc;
         return reduce_tree_mx(op, dtype, alg, out_dtype, out, out_scales, ins, in_scales, P, rank, n, resolve(stream));
     });
@@ -1986,10 +1881,7 @@ int fmi_dev_reduce_tree_mx_sr(int op, int dtype_arg, int alg, void* out, void* o
         if (int rc = mx_check_args("fmi_dev_reduce_tree_mx_sr", op, dtype_arg, alg, dtype, out_scales, &dtype)) return rc;
         if (int rc = mx_sr_check("fmi_dev_reduce_tree_mx_sr", seed, first, n)) return rc;
         if (int rc = check_peer_count(P)) return rc;  // op and dtype: mx_check_args above
-        if (rank < 0 || rank >= P) return fail(FMI_ERR_INVALID, "rank/root out of range");
-        if (!out || !ins || !in_scales) return fail(FMI_ERR_INVALID, "null buffer");
-        for (int p = 0; p < P; ++p)
-            if (!ins[p] || !in_scales[p]) return fail(FMI_ERR_INVALID, "null input bucket or scale array");
+        if (int rc = check_tree_buffers(P, rank, out && ins && in_scales, ins, in_scales)) return rc;
         if (int rc = require_device()) return rc;
         return reduce_tree_mx(op, dtype, alg, dtype, out, out_scales, ins, in_scales, P, rank, n, resolve(stream), seed, first);
     });

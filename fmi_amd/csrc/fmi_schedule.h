@@ -18,6 +18,7 @@
 // That is why a single pass over peers per round reproduces the message-passing order exactly.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <type_traits>
 #include <vector>
@@ -293,6 +294,47 @@ inline HostProgram build_host(int alg, int P) {
     HostProgram prog;
     build_into(prog, alg, P);
     return prog;
+}
+
+// The pairwise-pass execution of a host program (fmi_dev.hip run_program_stepwise), planned on the host: which
+// values the requested outputs depend on, and a temporary slot for each such step value. A slot is recycled right
+// after its value's last use (an output's never is), and a step takes its destination before it releases its
+// operands, so `nslots` is the peak number of temporaries live at once. Inputs (values < peers) take no slot.
+struct StepwisePlan {
+    std::vector<char> live;     // per value id: some output depends on it
+    std::vector<int32_t> slot;  // per value id: the slot of a live step value, -1 otherwise
+    int nslots = 0;
+};
+inline StepwisePlan plan_stepwise(const HostProgram& prog, const int32_t* out_value, int nouts) {
+    const int P = prog.peers;
+    const size_t nv = static_cast<size_t>(prog.nvalues());
+    StepwisePlan plan;
+    plan.live.assign(nv, 0);
+    for (int k = 0; k < nouts; ++k) plan.live[out_value[k]] = 1;
+    for (int st = prog.nsteps - 1; st >= 0; --st)
+        if (plan.live[P + st]) plan.live[prog.step[st].a] = plan.live[prog.step[st].b] = 1;
+    std::vector<int32_t> last_use(nv, -1);
+    for (int st = 0; st < prog.nsteps; ++st) {
+        if (!plan.live[P + st]) continue;
+        last_use[prog.step[st].a] = st;
+        last_use[prog.step[st].b] = st;
+    }
+    for (int k = 0; k < nouts; ++k) last_use[out_value[k]] = prog.nsteps;  // outputs live to the end
+    plan.slot.assign(nv, -1);
+    std::vector<int32_t> free_slots;
+    for (int st = 0; st < prog.nsteps; ++st) {
+        if (!plan.live[P + st]) continue;
+        if (!free_slots.empty()) {
+            plan.slot[P + st] = free_slots.back();
+            free_slots.pop_back();
+        } else {
+            plan.slot[P + st] = plan.nslots++;
+        }
+        const int32_t a = prog.step[st].a, b = prog.step[st].b;
+        if (a >= P && last_use[a] == st) free_slots.push_back(plan.slot[a]);
+        if (b >= P && b != a && last_use[b] == st) free_slots.push_back(plan.slot[b]);
+    }
+    return plan;
 }
 
 }  // namespace fmi::sched

@@ -381,6 +381,112 @@ def test_blocked_program_as_first_call_of_a_process(device):
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
 
 
+_SCRATCH_ORDER = """
+import numpy as np, fmi_amd
+from fmi_amd import Alg, Bucket, DType, Op, Stream, Tune
+from oracle import fmi_oracle as orc
+from tests import _fp8 as F, _fp8_scaled as FS, _half as H, _half_acc as HA
+from tests.test_gpu_parity import assert_bit_equal, inputs
+fmi_amd.init(0)
+A, B = Stream(), Stream()
+checks = []   # (check, output bucket, expected, what); every bucket stays referenced until the end
+
+def off16(host):   # a bucket one element off 16-B alignment
+    b = Bucket(host.size + 1, host.dtype)
+    b.upload(np.concatenate([np.zeros(1, host.dtype), host]))
+    return b, b.view(1, host.size)
+
+def f32_bits(got, want, what):
+    assert_bit_equal(got, want, what)
+
+def arena_unaligned(stream, seed, what):   # pairwise passes over the scratch arena
+    P, n, rank = 5, 1000, 3
+    xs = [inputs(np.float32, n, p, seed=seed) for p in range(P)]
+    ins = [off16(x) for x in xs]
+    out = off16(np.full(n, 1.5, np.float32))
+    fmi_amd.reduce_tree(Op.SUM, Alg.ALLREDUCE, out[1], [v for _, v in ins], rank=rank, stream=stream)
+    checks.append((f32_bits, out[1], orc.allreduce(xs, orc.op_sum)[0][rank], what, ins, out))
+
+def arena_blocked(stream, seed, what):   # block launches whose block values are arena temporaries
+    P, n, root = 40, 70000, 7
+    xs = [inputs(np.float32, n, p, seed=seed) for p in range(P)]
+    ins = [Bucket.from_numpy(x) for x in xs]
+    out = Bucket.from_numpy(np.full(n, 1.5, np.float32))
+    old = fmi_amd.tune_get(Tune.BLOCKS_ONE_PASS)
+    fmi_amd.tune_set(Tune.BLOCKS_ONE_PASS, 0)
+    try:
+        fmi_amd.reduce_tree(Op.SUM, Alg.REDUCE, out, ins, rank=root, stream=stream)
+    finally:
+        fmi_amd.tune_set(Tune.BLOCKS_ONE_PASS, old)
+    checks.append((f32_bits, out, orc.reduce(xs, orc.op_sum, root=root)[0], what, ins))
+
+def acc32(stream, n, seed, what):   # bf16 with f32 accumulation beyond 16 peers: the f32 temporaries
+    P = 17
+    xs = [H.inputs("bf16", n, seed, p) for p in range(P)]
+    ins = [Bucket(n, DType.BF16) for _ in range(P)]
+    for b, x in zip(ins, xs):
+        b.upload(x)
+    out = Bucket(n, DType.BF16)
+    out.upload(np.full(n, 0x5555, np.uint16))
+    fmi_amd.reduce_tree(Op.SUM, Alg.REDUCE, out, ins, rank=0, stream=stream, accumulate_f32=True)
+    want = HA.expected_acc("reduce", "bf16", "sum", xs, 0)[0]
+    checks.append((lambda g, w, t: H.assert_bits(g.view(np.uint16), w, "bf16", "sum", t), out, want, what, ins))
+
+def scaled(stream, seed, what):   # the scaled E4M3 sum beyond 16 peers: the same temporaries
+    P, n = 17, 1000
+    xs = [F.synthetic("e4m3", n, seed, p) for p in range(P)]
+    ins = [Bucket(n, DType.F8E4M3) for _ in range(P)]
+    for b, x in zip(ins, xs):
+        b.upload(x)
+    out = Bucket(n, DType.F8E4M3)
+    out.upload(np.full(n, 0x55, np.uint8))
+    s, t = FS.scales(P), FS.T_OUT
+    sb, tb = Bucket.from_numpy(s), Bucket.from_numpy(np.array([t], np.float32))
+    fmi_amd.reduce_tree_scaled(Alg.REDUCE, out, ins, sb, tb, None, rank=0, stream=stream)
+    want = FS.expected_scaled("reduce", "e4m3", xs, s, t, "same", 0)[0]
+    checks.append((lambda g, w, t_: FS.assert_out(g, w, "e4m3", "same", t_), out, want, what, ins, sb, tb))
+
+def compare():
+    A.sync()
+    B.sync()
+    for c in checks:
+        c[0](c[1].numpy(), c[2], c[3])
+    n = len(checks)
+    checks.clear()
+    return n
+
+# no synchronisation between these calls
+arena_unaligned(A, 11, "first use of the arena, stream A")
+arena_blocked(B, 12, "the arena grows on stream B under A's work")
+arena_unaligned(A, 13, "the grown arena again on stream A")
+acc32(A, 1000, 14, "first use of the f32 temporaries, stream A")
+acc32(B, 5000, 15, "the f32 temporaries grow on stream B under A's work")
+scaled(A, 16, "the scaled call shares the f32 temporaries, stream A")
+assert compare() == 6
+fmi_amd.finalize()
+fmi_amd.init(0)
+arena_unaligned(A, 17, "the arena after a re-init")
+arena_blocked(B, 18, "the blocked program after a re-init")
+acc32(A, 1000, 19, "the f32 temporaries after a re-init")
+scaled(B, 20, "the scaled call after a re-init")
+assert compare() == 4
+print("ok")
+"""
+
+
+def test_scratch_order_across_streams_growth_and_reinit(device):
+    """The library's two scratch buffers (the P-way arena, the f32 temporaries) from a fresh process, so that the
+    first allocation, the growth and the re-use are all forced: calls on two streams with no synchronisation between
+    them, a larger call on the other stream growing each buffer while the first stream's work may still be in flight,
+    then finalize, init and every kind of call again. Every output bit for bit against the oracle at the end."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _SCRATCH_ORDER], cwd=root, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-1000:], r.stderr[-3000:])
+
+
 @pytest.mark.parametrize("cap", [0, 4, 32, 96, 256])
 def test_fused_occupancy_cap_keeps_bits(device, cap):
     """FMI_TUNE_FUSED_INFLIGHT_KIB only reserves LDS to cap residency: results stay bit-exact (multi-wave
