@@ -107,23 +107,42 @@ class HipEngine:
 
     def reduce_tree_mx(self, op: Op, alg: Alg, out: torch.Tensor, out_scales: Optional[torch.Tensor],
                        ins: Sequence[torch.Tensor], in_scales: Sequence[torch.Tensor], rank: int = 0,
-                       seed: Optional[torch.Tensor] = None, first: int = 0) -> None:
+                       seed: Optional[torch.Tensor] = None, first: int = 0, dtype: Optional[DType] = None,
+                       n: Optional[int] = None) -> None:
         """The sum or mean of block-scaled (MX) float8 tensors (fmi_dev_reduce_tree_mx): `ins` are float8_e4m3fn /
         float8_e5m2 tensors, `in_scales` their float8_e8m0fnu (or uint8) scale tensors of ceil(n / 32) elements; `out` is
         a tensor of the inputs' dtype with `out_scales`, or of float32 with out_scales None. MXFP4: `ins` are
         float4_e2m1fn_x2 tensors (two elements per tensor element, so n = 2 * numel and a float32 `out` holds 2 * numel
-        values). seed: a one-element int64 / uint64 device tensor selects stochastic rounding
+        values). MXFP6: torch has no 6-bit dtype, so `ins` are uint8 tensors of the packed bytes with the keywords
+        dtype=DType.F6E2M3 / DType.F6E3M2 and n=the element count (ceil(3 n / 4) bytes each); `out` is such a uint8
+        tensor with `out_scales`, or a float32 tensor of n values. seed: a one-element int64 / uint64 device tensor selects stochastic rounding
         (fmi_dev_reduce_tree_mx_sr; `out` of the inputs' dtype): its 64 bits, as they are, are the Philox key, read by the
         kernel; `first`, a multiple of 32, is the stream position of element 0."""
         import ctypes
-        dtype = _dtype(ins[0])
-        if dtype not in (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1):
-            raise TypeError(f"reduce_tree_mx needs float8_e4m3fn, float8_e5m2 or float4_e2m1fn_x2 inputs, got {ins[0].dtype}")
-        per = 2 if dtype == DType.F4E2M1 else 1  # elements per tensor element
-        n = per * ins[0].numel()
-        if any(t.dtype != ins[0].dtype or t.numel() != ins[0].numel() or not t.is_contiguous() for t in ins) or \
-                out.numel() * (per if out.dtype == ins[0].dtype else 1) != n:
-            raise ValueError("reduce_tree_mx: contiguous inputs of one dtype and of out's length")
+        fp6 = dtype is not None and DType(dtype) in (DType.F6E2M3, DType.F6E3M2)
+        if dtype is not None and not fp6:
+            raise TypeError("reduce_tree_mx: the dtype keyword names the packed 6-bit types alone (DType.F6E2M3 / DType.F6E3M2)")
+        if fp6:
+            dtype = DType(dtype)
+            if ins[0].dtype != torch.uint8 or n is None or int(n) < 0:
+                raise TypeError("reduce_tree_mx: MXFP6 inputs are uint8 tensors of packed bytes with the element count n=")
+            n = int(n)
+            nbytes = (3 * n + 3) // 4
+            if any(t.dtype != torch.uint8 or t.numel() != nbytes or not t.is_contiguous() for t in ins) or \
+                    out.numel() != (nbytes if out.dtype == torch.uint8 else n):
+                raise ValueError(f"reduce_tree_mx: contiguous uint8 inputs of ceil(3 n / 4) = {nbytes} bytes and an out of that size "
+                                 f"(or of n float32 values)")
+        else:
+            if n is not None:
+                raise TypeError("reduce_tree_mx: the n keyword goes with dtype=DType.F6E2M3 / DType.F6E3M2 alone")
+            dtype = _dtype(ins[0])
+            if dtype not in (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1):
+                raise TypeError(f"reduce_tree_mx needs float8_e4m3fn, float8_e5m2 or float4_e2m1fn_x2 inputs, got {ins[0].dtype}")
+            per = 2 if dtype == DType.F4E2M1 else 1  # elements per tensor element
+            n = per * ins[0].numel()
+            if any(t.dtype != ins[0].dtype or t.numel() != ins[0].numel() or not t.is_contiguous() for t in ins) or \
+                    out.numel() * (per if out.dtype == ins[0].dtype else 1) != n:
+                raise ValueError("reduce_tree_mx: contiguous inputs of one dtype and of out's length")
         if out.dtype not in (ins[0].dtype, torch.float32) or not out.is_contiguous():
             raise ValueError("reduce_tree_mx: `out` is a contiguous tensor of the inputs' dtype or of float32")
         if len(in_scales) != len(ins):
@@ -149,7 +168,7 @@ class HipEngine:
             _lib.call("fmi_dev_reduce_tree_mx_sr", int(op), int(dtype), int(alg), out.data_ptr(), out_scales.data_ptr(), ptrs,
                       sptrs, seed.data_ptr(), int(first), len(ins), rank, n, self._stream())
             return
-        _lib.call("fmi_dev_reduce_tree_mx", int(op), int(dtype), int(alg), int(_dtype(out)), out.data_ptr(),
+        _lib.call("fmi_dev_reduce_tree_mx", int(op), int(dtype), int(alg), int(dtype if out.dtype == ins[0].dtype else DType.F32), out.data_ptr(),
                   out_scales.data_ptr() if out_scales is not None else None, ptrs, sptrs, len(ins), rank, n,
                   self._stream())
 

@@ -151,7 +151,7 @@ class Comm:
         over the ranks of `send` under its block scales `send_scales` (F8E8M0, ceil(n / 32) bytes), in the reference's
         order, into `recv` on every rank: an F32 bucket (recv_scales None), or a bucket of send's dtype requantized
         block by block with its scale bytes in `recv_scales`. The wire carries the element bytes and the scale bytes.
-        F4E2M1 buckets (MXFP4) travel packed, at half the element bytes.
+        F4E2M1 buckets (MXFP4) travel packed, at half the element bytes, F6E2M3 / F6E3M2 buckets (MXFP6) at three quarters.
         seed: a U64 bucket of one element selects stochastic rounding (fmi_comm_allreduce_mx_sr; `recv` of send's dtype):
         every rank holds the same value in it and passes the same `first`, a multiple of 32, and every rank's result is
         device.reduce_tree_mx's over the ranks' buckets at that (seed, first)."""
@@ -193,8 +193,8 @@ class Comm:
             raise ValueError("allreduce_host: arrays must share dtype and size")
         if not (send.flags.c_contiguous and recv.flags.c_contiguous):
             raise ValueError("allreduce_host: arrays must be contiguous")
-        if dtype is not None and DType(dtype) == DType.F4E2M1:
-            raise ValueError("allreduce_host: F4E2M1 is valid only in the MX calls")
+        if dtype is not None and DType(dtype) in (DType.F4E2M1, DType.F6E2M3, DType.F6E3M2):
+            raise ValueError(f"allreduce_host: {DType(dtype).name} is valid only in the MX calls")
         alg = Alg.REDUCE_LTR if ordered else Alg.ALLREDUCE
         arg = acc_dtype(dtype_of(send) if dtype is None else dtype, accumulate_f32)
         _lib.call("fmi_comm_allreduce_host", self.handle, int(op), arg, int(alg), int(path),

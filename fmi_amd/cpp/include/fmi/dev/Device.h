@@ -8,6 +8,7 @@
 #define FMI_AMD_DEV_DEVICE_H
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -252,6 +253,79 @@ static_assert(sizeof(float4_e2m1x2) == 1 && std::is_trivially_copyable_v<float4_
 // The bytes of an MXFP4 bucket of n elements.
 inline std::size_t fp4_bytes(std::size_t n) { return (n + 1) / 2; }
 
+// One byte of an MXFP6 bucket (OCP FP6, six bits per element: bit 5 the sign, no inf, no NaN; the bucket is a
+// little-endian bit string with element i in bits 6 i .. 6 i + 5, so four elements are three bytes and n elements
+// fp6_bytes(n)). Tag types with no arithmetic: only the MX calls below take buckets of them (FMI_F6E2M3 / FMI_F6E3M2 are
+// valid nowhere else), with the ELEMENT count given explicitly. widen / narrow are the library's definition of a code's
+// value on the host: narrow rounds to nearest with ties to the even code, keeps the sign, and is defined for finite |f|
+// at most the largest element (7.5 for E2M3, 28 for E3M2).
+namespace detail {
+template <int M>  // mantissa bits: 3 is E2M3 (bias 1), 2 is E3M2 (bias 3)
+struct fp6_code {
+    static constexpr int emin = M == 3 ? 0 : -2;
+    static float widen(std::uint8_t code) {
+        const int e = (code & 31) >> M, m = code & ((1 << M) - 1);
+        const float v = e == 0 ? std::ldexp(static_cast<float>(m), emin - M) : std::ldexp(static_cast<float>((1 << M) + m), e - 1 + emin - M);
+        return (code & 32) ? -v : v;
+    }
+    static std::uint8_t narrow(float f) {
+        const float a = std::fabs(f);
+        int e = 0;
+        std::frexp(a, &e);  // a = x * 2^e, 0.5 <= x < 1: the exponent of |f| is e - 1
+        const int ex = a == 0.0f || e - 1 < emin ? emin : e - 1;
+        const float t = std::ldexp(a, M - ex);  // |f| in grid steps: exact
+        const float k = std::floor(t), frac = t - k;
+        const unsigned ki = static_cast<unsigned>(k);
+        const unsigned up = frac > 0.5f || (frac == 0.5f && (ki & 1u));
+        return static_cast<std::uint8_t>((static_cast<unsigned>(ex - emin) << M) + ki + up + (std::signbit(f) ? 32u : 0u));
+    }
+};
+}  // namespace detail
+struct float6_e2m3_packed : detail::fp6_code<3> {
+    std::uint8_t bits = 0;
+};
+struct float6_e3m2_packed : detail::fp6_code<2> {
+    std::uint8_t bits = 0;
+};
+inline bool operator==(float6_e2m3_packed a, float6_e2m3_packed b) { return a.bits == b.bits; }
+inline bool operator==(float6_e3m2_packed a, float6_e3m2_packed b) { return a.bits == b.bits; }
+static_assert(sizeof(float6_e2m3_packed) == 1 && sizeof(float6_e3m2_packed) == 1 && std::is_trivially_copyable_v<float6_e2m3_packed> &&
+                  std::is_trivially_copyable_v<float6_e3m2_packed>,
+              "a packed FP6 byte is one raw byte");
+template <class A>
+inline constexpr bool fp6_packed_v = std::is_same_v<A, float6_e2m3_packed> || std::is_same_v<A, float6_e3m2_packed>;
+template <class A>
+constexpr int fp6_dtype() {
+    static_assert(fp6_packed_v<A>, "Dev::float6_e2m3_packed or Dev::float6_e3m2_packed");
+    return std::is_same_v<A, float6_e2m3_packed> ? FMI_F6E2M3 : FMI_F6E3M2;
+}
+// The bytes of an MXFP6 bucket of n elements.
+inline std::size_t fp6_bytes(std::size_t n) { return n / 4 * 3 + (n % 4 * 3 + 3) / 4; }
+// Codes (one per element, 0..63) into the bucket's bytes and back; the last byte's unused high bits are written 0.
+template <class A>
+inline std::vector<A> fp6_pack(const std::vector<std::uint8_t>& codes) {
+    static_assert(fp6_packed_v<A>, "fp6_pack: Dev::float6_e2m3_packed or Dev::float6_e3m2_packed bytes");
+    std::vector<A> out(fp6_bytes(codes.size()));
+    for (std::size_t i = 0; i < codes.size(); ++i) {
+        const unsigned v = static_cast<unsigned>(codes[i] & 63u) << (6 * i % 8);
+        out[6 * i / 8].bits = static_cast<std::uint8_t>(out[6 * i / 8].bits | v);
+        if (v >> 8) out[6 * i / 8 + 1].bits = static_cast<std::uint8_t>(out[6 * i / 8 + 1].bits | (v >> 8));
+    }
+    return out;
+}
+template <class A>
+inline std::vector<std::uint8_t> fp6_unpack(const std::vector<A>& packed, std::size_t n) {
+    static_assert(fp6_packed_v<A>, "fp6_unpack: Dev::float6_e2m3_packed or Dev::float6_e3m2_packed bytes");
+    if (packed.size() != fp6_bytes(n)) throw std::runtime_error("Dev::fp6_unpack: n elements are fp6_bytes(n) bytes");
+    std::vector<std::uint8_t> codes(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        unsigned w = packed[6 * i / 8].bits;
+        if (6 * i % 8 > 2) w |= static_cast<unsigned>(packed[6 * i / 8 + 1].bits) << 8;
+        codes[i] = static_cast<std::uint8_t>((w >> (6 * i % 8)) & 63u);
+    }
+    return codes;
+}
+
 // The float element types narrower than float: their values are held and scaled (the mean) in float.
 template <class A>
 inline constexpr bool narrow_float_v = std::is_same_v<A, half> || std::is_same_v<A, bfloat16> ||
@@ -287,7 +361,7 @@ constexpr bool device_type = dtype_of<A>() >= 0;
 // What a Bucket can hold: the device element types, and the scale bytes of MX buckets and the packed bytes of MXFP4
 // buckets, which only the MX calls take.
 template <class A>
-constexpr bool bucket_storage = device_type<A> || std::is_same_v<A, float8_e8m0> || std::is_same_v<A, float4_e2m1x2>;
+constexpr bool bucket_storage = device_type<A> || std::is_same_v<A, float8_e8m0> || std::is_same_v<A, float4_e2m1x2> || fp6_packed_v<A>;
 
 // Select the device for this process (one process per GPU, as FMI runs one peer per process).
 inline void init(int device = 0) { check(fmi_dev_init(device), "fmi_dev_init"); }
@@ -488,20 +562,37 @@ inline void reduce_tree_mx(int op, int alg, Bucket<A>& out, Bucket<float8_e8m0>&
     detail::reduce_tree_mx(op, alg, dtype_of<A>(), out.data(), out_scales.data(), out.size(), ins, in_scales, rank, stream, &sr);
 }
 
-// float / Dev::half / Dev::bfloat16 data into an MX bucket and back (fmi_dev_mx_quantize / fmi_dev_mx_dequantize).
+namespace detail {
+// The C-ABI element type and the bucket's bytes for n elements: one byte per 8-bit float, fp6_bytes(n) for the FP6 tags.
+template <class A>
+constexpr int mx_dtype() {
+    if constexpr (fp6_packed_v<A>) return fp6_dtype<A>();
+    else return dtype_of<A>();
+}
+template <class A>
+inline std::size_t mx_bytes(std::size_t n) {
+    if constexpr (fp6_packed_v<A>) return fp6_bytes(n);
+    else return n;
+}
+}  // namespace detail
+
+// float / Dev::half / Dev::bfloat16 data into an MX bucket and back (fmi_dev_mx_quantize / fmi_dev_mx_dequantize). The
+// float side gives n: an MXFP6 bucket (Dev::float6_e2m3_packed / Dev::float6_e3m2_packed) holds fp6_bytes(n) bytes.
 template <class A, class S>
 inline void mx_quantize(Bucket<A>& out, Bucket<float8_e8m0>& out_scales, const Bucket<S>& src, fmi_stream_t stream = nullptr) {
-    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>, "mx_quantize: Dev::float8_e4m3 or Dev::float8_e5m2 elements");
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2> || fp6_packed_v<A>,
+                  "mx_quantize: Dev::float8_e4m3, Dev::float8_e5m2 or packed FP6 elements");
     static_assert(std::is_same_v<S, float> || std::is_same_v<S, half> || std::is_same_v<S, bfloat16>, "mx_quantize: float, Dev::half or Dev::bfloat16 source");
-    if (out.size() != src.size() || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
-    check(fmi_dev_mx_quantize(dtype_of<A>(), out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), stream), "fmi_dev_mx_quantize");
+    if (out.size() != detail::mx_bytes<A>(src.size()) || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
+    check(fmi_dev_mx_quantize(detail::mx_dtype<A>(), out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), stream), "fmi_dev_mx_quantize");
 }
 template <class A, class S>
 inline void mx_quantize(Bucket<A>& out, Bucket<float8_e8m0>& out_scales, const Bucket<S>& src, fmi_stream_t stream, const Sr& sr) {
-    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>, "mx_quantize: Dev::float8_e4m3 or Dev::float8_e5m2 elements");
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2> || fp6_packed_v<A>,
+                  "mx_quantize: Dev::float8_e4m3, Dev::float8_e5m2 or packed FP6 elements");
     static_assert(std::is_same_v<S, float> || std::is_same_v<S, half> || std::is_same_v<S, bfloat16>, "mx_quantize: float, Dev::half or Dev::bfloat16 source");
-    if (out.size() != src.size() || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
-    check(fmi_dev_mx_quantize_sr(dtype_of<A>(), out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), detail::sr_seed(sr), sr.first,
+    if (out.size() != detail::mx_bytes<A>(src.size()) || out_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_quantize: size mismatch");
+    check(fmi_dev_mx_quantize_sr(detail::mx_dtype<A>(), out.data(), out_scales.data(), dtype_of<S>(), src.data(), src.size(), detail::sr_seed(sr), sr.first,
                                  stream),
           "fmi_dev_mx_quantize_sr");
 }
@@ -509,21 +600,23 @@ inline void mx_quantize(Bucket<A>& out, Bucket<float8_e8m0>& out_scales, const B
 template <class A>
 inline void mx_quantize_sr_host(std::vector<A>& out, std::vector<float8_e8m0>& out_scales, const std::vector<float>& src, std::uint64_t seed,
                                 std::uint64_t first = 0) {
-    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2> || std::is_same_v<A, float4_e2m1x2>,
-                  "mx_quantize_sr_host: Dev::float8_e4m3, Dev::float8_e5m2 or Dev::float4_e2m1x2 elements");
-    constexpr bool fp4 = std::is_same_v<A, float4_e2m1x2>;
-    out.assign(fp4 ? fp4_bytes(src.size()) : src.size(), A{});
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2> || std::is_same_v<A, float4_e2m1x2> || fp6_packed_v<A>,
+                  "mx_quantize_sr_host: Dev::float8_e4m3, Dev::float8_e5m2, Dev::float4_e2m1x2 or packed FP6 elements");
+    constexpr bool fp4 = std::is_same_v<A, float4_e2m1x2>, fp6 = fp6_packed_v<A>;
+    out.assign(fp4 ? fp4_bytes(src.size()) : fp6 ? fp6_bytes(src.size()) : src.size(), A{});
     out_scales.assign(mx_blocks(src.size()), float8_e8m0{});
     int dtype = FMI_F4E2M1;
-    if constexpr (!fp4) dtype = dtype_of<A>();
+    if constexpr (fp6) dtype = fp6_dtype<A>();
+    else if constexpr (!fp4) dtype = dtype_of<A>();
     check(fmi_host_mx_quantize_sr(dtype, out.data(), out_scales.data(), src.data(), src.size(), seed, first), "fmi_host_mx_quantize_sr");
 }
 template <class D, class A>
 inline void mx_dequantize(Bucket<D>& dst, const Bucket<A>& src, const Bucket<float8_e8m0>& src_scales, fmi_stream_t stream = nullptr) {
-    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2>, "mx_dequantize: Dev::float8_e4m3 or Dev::float8_e5m2 elements");
+    static_assert(std::is_same_v<A, float8_e4m3> || std::is_same_v<A, float8_e5m2> || fp6_packed_v<A>,
+                  "mx_dequantize: Dev::float8_e4m3, Dev::float8_e5m2 or packed FP6 elements");
     static_assert(std::is_same_v<D, float> || std::is_same_v<D, half> || std::is_same_v<D, bfloat16>, "mx_dequantize: float, Dev::half or Dev::bfloat16 destination");
-    if (dst.size() != src.size() || src_scales.size() != mx_blocks(src.size())) throw std::runtime_error("Dev::mx_dequantize: size mismatch");
-    check(fmi_dev_mx_dequantize(dtype_of<D>(), dst.data(), dtype_of<A>(), src.data(), src_scales.data(), src.size(), stream), "fmi_dev_mx_dequantize");
+    if (src.size() != detail::mx_bytes<A>(dst.size()) || src_scales.size() != mx_blocks(dst.size())) throw std::runtime_error("Dev::mx_dequantize: size mismatch");
+    check(fmi_dev_mx_dequantize(dtype_of<D>(), dst.data(), detail::mx_dtype<A>(), src.data(), src_scales.data(), dst.size(), stream), "fmi_dev_mx_dequantize");
 }
 
 // MXFP4 (fmi_dev_reduce_tree_mx at FMI_F4E2M1): buckets of Dev::float4_e2m1x2 bytes, fp4_bytes(n) of them for n
@@ -595,6 +688,57 @@ inline void mx_dequantize(Bucket<D>& dst, const Bucket<float4_e2m1x2>& src, cons
     if (src.size() != fp4_bytes(dst.size()) || src_scales.size() != mx_blocks(dst.size())) throw std::runtime_error("Dev::mx_dequantize: size mismatch");
     check(fmi_dev_mx_dequantize(dtype_of<D>(), dst.data(), FMI_F4E2M1, src.data(), src_scales.data(), dst.size(), stream), "fmi_dev_mx_dequantize");
 }
+
+// MXFP6 (fmi_dev_reduce_tree_mx at FMI_F6E2M3 / FMI_F6E3M2): buckets of Dev::float6_e2m3_packed / Dev::float6_e3m2_packed
+// bytes, fp6_bytes(n) of them for n ELEMENTS, which every call takes explicitly or from its float side; scale bytes as
+// above. A: one of the two tag types.
+namespace detail {
+template <class A>
+inline void reduce_tree_mxfp6(int op, int alg, int out_dtype, void* out, void* out_scales, std::size_t n, const std::vector<const Bucket<A>*>& ins,
+                              const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank, fmi_stream_t stream, const Sr* sr = nullptr) {
+    if (ins.empty() || ins.size() > static_cast<std::size_t>(std::numeric_limits<int>::max()) || in_scales.size() != ins.size())
+        throw std::runtime_error("Dev::reduce_tree_mx: need at least one input bucket and one scale bucket per input");
+    std::vector<const void*> ptrs, sptrs;
+    for (std::size_t p = 0; p < ins.size(); ++p) {
+        if (!ins[p] || ins[p]->size() != fp6_bytes(n)) throw std::runtime_error("Dev::reduce_tree_mx: an MXFP6 bucket of n elements holds fp6_bytes(n) bytes");
+        if (!in_scales[p] || in_scales[p]->size() != mx_blocks(n))
+            throw std::runtime_error("Dev::reduce_tree_mx: a scale bucket holds (n + 31) / 32 bytes");
+        ptrs.push_back(ins[p]->data());
+        sptrs.push_back(in_scales[p]->data());
+    }
+    if (sr) {
+        check(fmi_dev_reduce_tree_mx_sr(op, fp6_dtype<A>(), alg, out, out_scales, ptrs.data(), sptrs.data(), sr_seed(*sr), sr->first,
+                                        static_cast<int>(ins.size()), rank, n, stream),
+              "fmi_dev_reduce_tree_mx_sr");
+        return;
+    }
+    check(fmi_dev_reduce_tree_mx(op, fp6_dtype<A>(), alg, out_dtype, out, out_scales, ptrs.data(), sptrs.data(), static_cast<int>(ins.size()), rank, n,
+                                 stream),
+          "fmi_dev_reduce_tree_mx");
+}
+}  // namespace detail
+
+template <class A, std::enable_if_t<fp6_packed_v<A>, int> = 0>
+inline void reduce_tree_mx(int op, int alg, Bucket<A>& out, Bucket<float8_e8m0>& out_scales, std::size_t n, const std::vector<const Bucket<A>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank = 0, fmi_stream_t stream = nullptr) {
+    if (out.size() != fp6_bytes(n) || out_scales.size() != mx_blocks(n))
+        throw std::runtime_error("Dev::reduce_tree_mx: out holds fp6_bytes(n) bytes and out_scales (n + 31) / 32");
+    detail::reduce_tree_mxfp6<A>(op, alg, fp6_dtype<A>(), out.data(), out_scales.data(), n, ins, in_scales, rank, stream);
+}
+template <class A, std::enable_if_t<fp6_packed_v<A>, int> = 0>
+inline void reduce_tree_mx(int op, int alg, Bucket<A>& out, Bucket<float8_e8m0>& out_scales, std::size_t n, const std::vector<const Bucket<A>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank, fmi_stream_t stream, const Sr& sr) {
+    if (out.size() != fp6_bytes(n) || out_scales.size() != mx_blocks(n))
+        throw std::runtime_error("Dev::reduce_tree_mx: out holds fp6_bytes(n) bytes and out_scales (n + 31) / 32");
+    detail::reduce_tree_mxfp6<A>(op, alg, fp6_dtype<A>(), out.data(), out_scales.data(), n, ins, in_scales, rank, stream, &sr);
+}
+template <class A, std::enable_if_t<fp6_packed_v<A>, int> = 0>
+inline void reduce_tree_mx(int op, int alg, Bucket<float>& out, std::size_t n, const std::vector<const Bucket<A>*>& ins,
+                           const std::vector<const Bucket<float8_e8m0>*>& in_scales, int rank = 0, fmi_stream_t stream = nullptr) {
+    if (out.size() != n) throw std::runtime_error("Dev::reduce_tree_mx: a float output holds n elements");
+    detail::reduce_tree_mxfp6<A>(op, alg, FMI_F32, out.data(), nullptr, n, ins, in_scales, rank, stream);
+}
+// mx_quantize, mx_dequantize and mx_quantize_sr_host at the two tag types are the templates above (the float side gives n).
 
 // Untyped device scratch used by the channel algorithms for temporaries of device-resident buckets.
 class Scratch {

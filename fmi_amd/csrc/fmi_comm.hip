@@ -1838,10 +1838,12 @@ int allreduce_mx_device(Comm* c, int op, int dtype, int alg, int out_dtype, cons
     if (one_rank(*c->t))  // the P = 1 form: not a copy
         return reduce_tree_mx(op, dtype, alg, out_dtype, recv, recv_scales, &send, &send_scales, 1, 0, n, s, seed, first);
     static_assert(kShardAlign % 32 == 0, "shard boundaries are MX block (and so FP4 byte) boundaries");
+    static_assert(kShardAlign % 64 == 0 && kShardAlign * 3 / 4 % 16 == 0,
+                  "shard boundaries are FP6 block-pair boundaries: whole bytes, 16-B aligned (64 elements are 48 B)");
     const bool wide = out_dtype == FMI_F32;
     // Byte counts: eb per input shard (shard for the 8-bit floats; shard / 2 for FMI_F4E2M1, whole bytes and whole
-    // blocks because kShardAlign is even), ob per output shard, nb / nob for the buckets' first n elements. Only the last
-    // non-empty shard can have an odd TRUE length, and its kernel writes that byte's high nibble as 0.
+    // blocks because kShardAlign is even; shard * 3 / 4 for the 6-bit floats), ob per output shard, nb / nob for the buckets' first n elements. Only the last
+    // non-empty shard can have a ragged TRUE length, and its kernel writes the last byte's unused bits as 0.
     const ShardGrid g(*c->t, n);
     const size_t shard = g.shard;
     const size_t eb = mx_elem_bytes(dtype, shard), ob = wide ? shard * sizeof(float) : eb;

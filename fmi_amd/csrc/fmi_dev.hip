@@ -1776,7 +1776,7 @@ int mx_check_args(const char* who, int op, int dtype_arg, int alg, int out_dtype
     *dtype = storage_dtype(dtype_arg);
     if (!is_mx_dtype(*dtype))
         return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype_arg) + " is not FMI_F8E4M3 or FMI_F8E5M2 (MXFP8) or "
-                                         "FMI_F4E2M1 (MXFP4), the element types an MX bucket can have");
+                                         "FMI_F4E2M1 (MXFP4) or FMI_F6E2M3 or FMI_F6E3M2 (MXFP6), the element types an MX bucket can have");
     if (int rc = check_alg_out_dtype(w, "an MX reduction", alg, out_dtype, *dtype)) return rc;
     if (out_dtype != FMI_F32 && !out_scales)
         return fail(FMI_ERR_INVALID, w + "out_scales is NULL: an output of dtype " + std::to_string(out_dtype) +
@@ -1789,7 +1789,7 @@ static int mx_check_convert(const char* who, int dtype, const char* what, int wi
     const std::string w = std::string(who) + ": ";
     if (!is_mx_dtype(dtype))
         return fail(FMI_ERR_INVALID, w + "dtype " + std::to_string(dtype) + " is not FMI_F8E4M3 or FMI_F8E5M2 (MXFP8) or "
-                                         "FMI_F4E2M1 (MXFP4), the element types an MX bucket can have");
+                                         "FMI_F4E2M1 (MXFP4) or FMI_F6E2M3 or FMI_F6E3M2 (MXFP6), the element types an MX bucket can have");
     if (wide != FMI_F32 && wide != FMI_F16 && wide != FMI_BF16)
         return fail(FMI_ERR_INVALID, w + what + " " + std::to_string(wide) + " must be FMI_F32, FMI_F16 or FMI_BF16");
     return FMI_OK;

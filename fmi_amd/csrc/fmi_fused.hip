@@ -139,22 +139,25 @@ int launch_fused_scaled(int alg, int dtype, int out_dtype, int P, const PeerPtrs
     }
 }
 
-// The unit of one algorithm's four MX families: fmi_fused_mx_*.hip, _mx_sr_, _mxfp4_, _mxfp4_sr_.
+// The unit of one algorithm's six MX families: fmi_fused_mx_*.hip, _mx_sr_, _mxfp4_, _mxfp4_sr_, _mxfp6_, _mxfp6_sr_.
+// bits: the element's width, 8, 4 or 6.
 template <int ALG>
-MxUnit* mx_family(bool fp4, bool sr) {
-    if (fp4) return sr ? &mxfp4_unit<ALG, true> : &mxfp4_unit<ALG, false>;
+MxUnit* mx_family(int bits, bool sr) {
+    if (bits == 4) return sr ? &mxfp4_unit<ALG, true> : &mxfp4_unit<ALG, false>;
+    if (bits == 6) return sr ? &mxfp6_unit<ALG, true> : &mxfp6_unit<ALG, false>;
     return sr ? &mx_unit<ALG, true> : &mx_unit<ALG, false>;
 }
 
 int launch_fused_mx(int alg, int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s) {
-    const bool fp4 = dtype == FMI_F4E2M1, sr = mx.seed != nullptr;
+    const int bits = dtype == FMI_F4E2M1 ? 4 : is_fp6_dtype(dtype) ? 6 : 8;
+    const bool sr = mx.seed != nullptr;
     if (sr && out_dtype != dtype) return fail(FMI_ERR_INVALID, "fused MX stochastic-rounding launch: the output is the element type's");
     switch (alg) {
-        case sched::kAllreduce: return mx_family<sched::kAllreduce>(fp4, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
-        case sched::kReduce: return mx_family<sched::kReduce>(fp4, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
-        case sched::kReduceLtr: return mx_family<sched::kReduceLtr>(fp4, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
+        case sched::kAllreduce: return mx_family<sched::kAllreduce>(bits, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
+        case sched::kReduce: return mx_family<sched::kReduce>(bits, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
+        case sched::kReduceLtr: return mx_family<sched::kReduceLtr>(bits, sr)(dtype, out_dtype, P, ptrs, mx, n, s);
         default:
-            return fail(FMI_ERR_INVALID, std::string("fused ") + (sr ? "MX stochastic-rounding" : fp4 ? "MXFP4" : "MX") +
+            return fail(FMI_ERR_INVALID, std::string("fused ") + (sr ? "MX stochastic-rounding" : bits == 4 ? "MXFP4" : bits == 6 ? "MXFP6" : "MX") +
                                              " launch: no kernel for algorithm " + std::to_string(alg));
     }
 }

@@ -52,10 +52,21 @@ inline bool is_half_dtype(int dtype) { return dtype == FMI_F16 || dtype == FMI_B
 inline bool is_fp8_dtype(int dtype) { return dtype == FMI_F8E4M3 || dtype == FMI_F8E5M2; }
 // The element types an MX bucket can have: the two 8-bit floats and FMI_F4E2M1, which is valid in the MX calls ALONE
 // (two elements to a byte: mx_elem_bytes). Every other entry point refuses it on the host, naming it (refuse_fp4).
-inline bool is_mx_dtype(int dtype) { return is_fp8_dtype(dtype) || dtype == FMI_F4E2M1; }
-inline size_t mx_elem_bytes(int dtype, size_t n) { return dtype == FMI_F4E2M1 ? n / 2 + n % 2 : n; }
+// The same holds for the two 6-bit floats FMI_F6E2M3 and FMI_F6E3M2 (MXFP6: four elements to three bytes).
+inline bool is_fp6_dtype(int dtype) { return dtype == FMI_F6E2M3 || dtype == FMI_F6E3M2; }
+inline bool is_mx_dtype(int dtype) { return is_fp8_dtype(dtype) || dtype == FMI_F4E2M1 || is_fp6_dtype(dtype); }
+inline size_t mx_elem_bytes(int dtype, size_t n) {
+    if (is_fp6_dtype(dtype)) return n / 4 * 3 + (n % 4 * 3 + 3) / 4;  // ceil(3 n / 4) without the overflow of 3 n
+    return dtype == FMI_F4E2M1 ? n / 2 + n % 2 : n;
+}
+// refuse_fp4: the sub-byte element types, FMI_F4E2M1 and the two 6-bit floats.
 inline int refuse_fp4(int dtype_arg) {
-    if ((dtype_arg & ~FMI_ACC_F32) != FMI_F4E2M1) return FMI_OK;  // with or without the flag
+    const int st = dtype_arg & ~FMI_ACC_F32;  // with or without the flag
+    if (is_fp6_dtype(st))
+        return fail(FMI_ERR_INVALID, "dtype " + std::to_string(dtype_arg) + (st == FMI_F6E2M3 ? " (FMI_F6E2M3)" : " (FMI_F6E3M2)") +
+                                     " is valid only as the element type of the MX calls (fmi_dev_reduce_tree_mx, fmi_dev_mx_quantize, "
+                                     "fmi_dev_mx_dequantize, fmi_comm_allreduce_mx): 6-bit elements have no other kernel");
+    if (st != FMI_F4E2M1) return FMI_OK;
     return fail(FMI_ERR_INVALID, "dtype " + std::to_string(dtype_arg) + " (FMI_F4E2M1) is valid only as the element type of "
                                  "the MX calls (fmi_dev_reduce_tree_mx, fmi_dev_mx_quantize, fmi_dev_mx_dequantize, "
                                  "fmi_comm_allreduce_mx): 4-bit elements have no other kernel");
@@ -274,15 +285,20 @@ int launch_fused_mx(int alg, int dtype, int out_dtype, int P, const PeerPtrs& pt
 //   mx_unit<ALG, true>       both 8-bit floats, stochastic rounding     fmi_mx_impl.h, one fmi_fused_mx_sr_*.hip each
 //   mxfp4_unit<ALG, false>   FMI_F4E2M1, E2M1 and f32 output            fmi_mxfp4_impl.h, one fmi_fused_mxfp4_*.hip each
 //   mxfp4_unit<ALG, true>    FMI_F4E2M1, stochastic rounding            fmi_mxfp4_impl.h, one fmi_fused_mxfp4_sr_*.hip each
+//   mxfp6_unit<ALG, false>   FMI_F6E2M3 / FMI_F6E3M2, FP6 and f32 output fmi_mxfp6_impl.h, one fmi_fused_mxfp6_*.hip each
+//   mxfp6_unit<ALG, true>    FMI_F6E2M3 / FMI_F6E3M2, stochastic rounding fmi_mxfp6_impl.h, one fmi_fused_mxfp6_sr_*.hip each
 // A stochastic-rounding unit (mx.seed != nullptr) holds the element type's own output only: out_dtype == dtype.
-// n counts elements (FMI_F4E2M1: two to a byte).
+// n counts elements (FMI_F4E2M1: two to a byte; the 6-bit floats: four to three bytes).
 using MxUnit = int(int dtype, int out_dtype, int P, const PeerPtrs& ptrs, const MxArgs& mx, size_t n, hipStream_t s);
 template <int ALG, bool SR>
 MxUnit mx_unit;
 template <int ALG, bool SR>
 MxUnit mxfp4_unit;
+template <int ALG, bool SR>
+MxUnit mxfp6_unit;
 // fmi_dev_mx_dequantize / fmi_dev_mx_quantize (fmi_mx.hip), any alignment, one launch each. dtype: FMI_F8E4M3,
-// FMI_F8E5M2 or FMI_F4E2M1 (packed: n elements in ceil(n / 2) bytes); dst_dtype / src_dtype: FMI_F32, FMI_F16 or FMI_BF16 (FMI_ERR_INVALID otherwise).
+// FMI_F8E5M2, FMI_F4E2M1 (packed: n elements in ceil(n / 2) bytes) or FMI_F6E2M3 / FMI_F6E3M2 (packed: ceil(3 n / 4)
+// bytes); dst_dtype / src_dtype: FMI_F32, FMI_F16 or FMI_BF16 (FMI_ERR_INVALID otherwise).
 int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s);
 int launch_mx_quantize(int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s);
 // fmi_dev_mx_quantize_sr (fmi_mx.hip too): launch_mx_quantize with narrow_sr (fmi_mx_sr.h); seed one u64 in device memory, first the

@@ -11,7 +11,10 @@
 // widening and the integer-code narrowing of fmi_mxfp4_impl.h.
 // fmi_dev_mx_quantize_sr, which is also what a fmi_dev_reduce_tree_mx_sr call beyond the fused kernels ends with, is the
 // quantize kernels' SR instantiation: out = narrow_sr(fl32(S * 2^(127 - e_out)), r) (fmi_mx_sr.h).
+// FMI_F6E2M3 / FMI_F6E3M2 (four elements to three bytes): FOUR elements, three whole bytes, per thread and step; a block
+// of 32 elements is 8 threads and its amax three shuffles. The integer-code widening and narrowing of fmi_mxfp6_impl.h.
 #include "fmi_mxfp4_impl.h"
+#include "fmi_mxfp6_impl.h"
 
 namespace fmi::dev {
 namespace {
@@ -136,6 +139,77 @@ __global__ void __launch_bounds__(kBlock) mxfp4_quantize_kernel(uint8_t* out, ui
     }
 }
 
+// The 6-bit floats, M as in fmi_mxfp6_impl.h. n: elements; the bucket is ceil(3 n / 4) bytes. A thread takes FOUR
+// elements, three whole bytes, so nothing is sub-byte shared; the last thread of a ragged bucket reads and writes only
+// the bytes the bucket has, and the bits of the last byte beyond element n - 1 are ignored.
+template <int M, class D>
+__global__ void __launch_bounds__(kBlock) mxfp6_dequantize_kernel(D* dst, const uint8_t* src, const uint8_t* scales, size_t n) {
+    const size_t nquad = n / 4 + (n % 4 != 0), nbytes = n / 4 * 3 + (n % 4 * 3 + 3) / 4;
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < nquad; i += stride) {
+        uint32_t three = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (3 * i + k < nbytes) three |= static_cast<uint32_t>(src[3 * i + k]) << (8 * k);
+        const float sc = mx_scale32(scales[i / 8]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (4 * i + k < n) {
+                Lanes<float, 1> v;
+                v.v[0] = fp6_widen_sw<M>(three >> (6 * k)) * sc;
+                dst[4 * i + k] = to_storage<D>(v).v[0];
+            }
+    }
+}
+
+// SR: as mx_quantize_kernel's; a thread's elements 4 i .. 4 i + 3 lie in one Philox group because `first` is a multiple of 4.
+template <int M, class S, class... SR>
+__global__ void __launch_bounds__(kBlock) mxfp6_quantize_kernel(uint8_t* out, uint8_t* out_scales, const S* src, size_t n, SR... sr) {
+    constexpr bool kSr = sizeof...(SR) != 0;
+    const SrStream stream{sr...};
+    uint64_t seed = 0;
+    if constexpr (kSr) seed = *stream.seed;
+    const size_t nquad = n / 4 + (n % 4 != 0), nbytes = n / 4 * 3 + (n % 4 * 3 + 3) / 4;
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    const unsigned lane = threadIdx.x % 64;
+    // `wave0`: the first quad of this wave's 64 (eight blocks); the loop's condition is the wave's, not the lane's
+    for (size_t wave0 = static_cast<size_t>(blockIdx.x) * blockDim.x + (threadIdx.x - lane); wave0 < nquad; wave0 += stride) {
+        const size_t i = wave0 + lane;
+        float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // beyond the bucket: +0, whose code 0 is what the last byte's unused bits take
+        uint32_t A = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (4 * i + k < n) {
+                Lanes<S, 1> raw;
+                raw.v[0] = src[4 * i + k];
+                x[k] = to_value<float>(raw).v[0];
+            }
+            A = max(A, mx_abs_bits(x[k]));
+        }
+#pragma unroll
+        for (int d = 4; d > 0; d >>= 1) A = max(A, static_cast<uint32_t>(__shfl_xor(static_cast<int>(A), d, 64)));
+        const uint32_t e_out = mxfp6_scale_byte<M>(A);
+        const float inv = mx_inv_scale(e_out);
+        if (i < nquad) {
+            uint32_t c[4];
+            Philox4 W{};
+            if constexpr (kSr) W = philox4x32_10((stream.first + 4 * i) >> 3, seed);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if constexpr (kSr)
+                    c[k] = 4 * i + k < n ? fp6_narrow_sr<M>(x[k] * inv, sr_bits(W, stream.first + 4 * i + k)) : 0u;
+                else
+                    c[k] = fp6_narrow_sw<M>(x[k] * inv);
+            }
+            const uint32_t three = e_out == 255u ? 0u : fp6_pack4(c[0], c[1], c[2], c[3]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (3 * i + k < nbytes) out[3 * i + k] = static_cast<uint8_t>(three >> (8 * k));
+            if (lane % 8 == 0) out_scales[i / 8] = static_cast<uint8_t>(e_out);
+        }
+    }
+}
+
 unsigned grid_of(size_t n) { return static_cast<unsigned>(std::min(grid_for(n, kBlock), kGridCap)); }
 
 // f.template operator()<D>() for the non-MX side of a conversion: FMI_F32, FMI_F16 or FMI_BF16.
@@ -155,6 +229,15 @@ template <class... SR>
 int quantize(const char* who, int dtype, void* out, uint8_t* out_scales, int src_dtype, const void* src, size_t n, hipStream_t s, SR... sr) {
     constexpr bool kSr = sizeof...(SR) != 0;
     if (n == 0) return FMI_OK;
+    if (is_fp6_dtype(dtype))
+        return with_wide_dtype(who, "src_dtype", src_dtype, [&]<class S>() -> int {
+            const unsigned grid = grid_of(n / 4 + (n % 4 != 0));
+            if (dtype == FMI_F6E2M3)
+                mxfp6_quantize_kernel<3><<<grid, kBlock, 0, s>>>(static_cast<uint8_t*>(out), out_scales, static_cast<const S*>(src), n, sr...);
+            else
+                mxfp6_quantize_kernel<2><<<grid, kBlock, 0, s>>>(static_cast<uint8_t*>(out), out_scales, static_cast<const S*>(src), n, sr...);
+            return check_launch(kSr ? "MXFP6 stochastic-rounding quantize kernel launch" : "MXFP6 quantize kernel launch");
+        });
     if (dtype == FMI_F4E2M1)
         return with_wide_dtype(who, "src_dtype", src_dtype, [&]<class S>() -> int {
             mxfp4_quantize_kernel<<<grid_of(n / 2 + n % 2), kBlock, 0, s>>>(static_cast<uint8_t*>(out), out_scales, static_cast<const S*>(src), n,
@@ -173,6 +256,15 @@ int quantize(const char* who, int dtype, void* out, uint8_t* out_scales, int src
 
 int launch_mx_dequantize(int dst_dtype, void* dst, int dtype, const void* src, const uint8_t* scales, size_t n, hipStream_t s) {
     if (n == 0) return FMI_OK;
+    if (is_fp6_dtype(dtype))
+        return with_wide_dtype("fmi_dev_mx_dequantize", "dst_dtype", dst_dtype, [&]<class D>() -> int {
+            const unsigned grid = grid_of(n / 4 + (n % 4 != 0));
+            if (dtype == FMI_F6E2M3)
+                mxfp6_dequantize_kernel<3, D><<<grid, kBlock, 0, s>>>(static_cast<D*>(dst), static_cast<const uint8_t*>(src), scales, n);
+            else
+                mxfp6_dequantize_kernel<2, D><<<grid, kBlock, 0, s>>>(static_cast<D*>(dst), static_cast<const uint8_t*>(src), scales, n);
+            return check_launch("MXFP6 dequantize kernel launch");
+        });
     if (dtype == FMI_F4E2M1)
         return with_wide_dtype("fmi_dev_mx_dequantize", "dst_dtype", dst_dtype, [&]<class D>() -> int {
             mxfp4_dequantize_kernel<D><<<grid_of(n / 2 + n % 2), kBlock, 0, s>>>(static_cast<D*>(dst), static_cast<const uint8_t*>(src), scales, n);

@@ -1,8 +1,9 @@
 // fmi_host_mx_quantize_sr (include/fmi_dev.h): fmi_dev_mx_quantize_sr's quantization on host memory, from the functions
-// the kernels use (fmi_mx_sr.h, and the scale-byte rules of fmi_mx_impl.h / fmi_mxfp4_impl.h). Host code only: the
+// the kernels use (fmi_mx_sr.h, and the scale-byte rules of fmi_mx_impl.h / fmi_mxfp4_impl.h / fmi_mxfp6_impl.h). Host code only: the
 // kernels of the device call are the quantize kernels' SR instantiations (fmi_mx.hip).
 //   per block of 32: A = umax bits(|S|), e_out = the block's scale byte, out = narrow_sr(fl32(S * 2^(127 - e_out)), r)
 #include "fmi_mxfp4_impl.h"
+#include "fmi_mxfp6_impl.h"
 
 namespace fmi::dev {
 namespace {
@@ -35,7 +36,21 @@ int host_mx_quantize_sr(int dtype, void* out, uint8_t* out_scales, const float* 
         const size_t len = std::min<size_t>(32, n - i0);
         uint8_t* scale = out_scales + i0 / 32;
         const auto fp8_store = [&](size_t i, uint32_t c) { o[i] = static_cast<uint8_t>(c == ~0u ? 0x7Fu : c); };
-        if (dtype == FMI_F4E2M1) {
+        if (is_fp6_dtype(dtype)) {
+            // i0 is a multiple of 4: whole bytes from 3 i0 / 4 on; zeroed first, so the last byte's unused bits stay 0
+            for (size_t k = i0 / 4 * 3; k < mx_elem_bytes(dtype, i0 + len); ++k) o[k] = 0;
+            const auto fp6_store = [&](size_t i, uint32_t c) {
+                const uint32_t v = (c == ~0u ? 0u : c) << (6 * i % 8);  // up to 12 bits over two bytes
+                o[6 * i / 8] = static_cast<uint8_t>(o[6 * i / 8] | v);
+                if (v >> 8) o[6 * i / 8 + 1] = static_cast<uint8_t>(o[6 * i / 8 + 1] | (v >> 8));
+            };
+            if (dtype == FMI_F6E2M3)
+                host_block(src, i0, len, scale, seed, first, [](uint32_t A) { return mxfp6_scale_byte<3>(A); },
+                           [](float y, uint32_t r) { return fp6_narrow_sr<3>(y, r); }, fp6_store);
+            else
+                host_block(src, i0, len, scale, seed, first, [](uint32_t A) { return mxfp6_scale_byte<2>(A); },
+                           [](float y, uint32_t r) { return fp6_narrow_sr<2>(y, r); }, fp6_store);
+        } else if (dtype == FMI_F4E2M1) {
             for (size_t k = i0 / 2; k < (i0 + len + 1) / 2; ++k) o[k] = 0;  // i0 is even: whole bytes, the odd last high nibble 0
             host_block(src, i0, len, scale, seed, first, [](uint32_t A) { return mxfp4_scale_byte(A); },
                        [](float y, uint32_t r) { return fp4_narrow_sr(y, r); },

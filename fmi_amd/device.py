@@ -56,6 +56,16 @@ class DType(enum.IntEnum):
     # 3:0 of byte k, element 2k + 1 in bits 7:4), so a Bucket of n ELEMENTS holds (n + 1) // 2 bytes. Valid in the MX
     # calls alone (reduce_tree_mx, mx_quantize, mx_dequantize, Comm.allreduce_mx): every other call raises ValueError.
     F4E2M1 = 15
+    # The two OCP 6-bit floats, the elements of an MXFP6 bucket: four elements to three bytes over np.uint8 (element i in
+    # bits 6 i .. 6 i + 5 of the little-endian bit string), so a Bucket of n ELEMENTS holds (3 n + 3) // 4 bytes. Valid
+    # in the MX calls alone, like F4E2M1.
+    F6E2M3 = 16
+    F6E3M2 = 17
+
+
+FP6_DTYPES = (DType.F6E2M3, DType.F6E3M2)
+# what an MX bucket's elements can be
+MX_DTYPES = (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1) + FP6_DTYPES
 
 
 # fmi_dev.h's FMI_ACC_F32: ORed into the dtype argument of a P-way call on F16 / BF16 / F8E4M3 / F8E5M2 buckets, the program's values
@@ -106,21 +116,26 @@ NP_DTYPE = {DType.F32: np.float32, DType.F64: np.float64, DType.I32: np.int32, D
 # numpy has no bfloat16 and no 8-bit floats: a BF16 bucket moves its elements' raw bits as np.uint16, an F8E4M3 /
 # F8E5M2 bucket as np.uint8 (np.uint8 alone keeps meaning U8)
 _HOST_DTYPE = {**NP_DTYPE, DType.BF16: np.uint16, DType.F8E4M3: np.uint8, DType.F8E5M2: np.uint8, DType.F8E8M0: np.uint8,
-               DType.F4E2M1: np.uint8}
+               DType.F4E2M1: np.uint8, DType.F6E2M3: np.uint8, DType.F6E3M2: np.uint8}
 
 
 def storage_bytes(dtype: "DType", n: int) -> int:
-    """The bytes a bucket of n elements takes: n times the element size, or (n + 1) // 2 for the packed F4E2M1."""
+    """The bytes a bucket of n elements takes: n times the element size, (n + 1) // 2 for the packed F4E2M1, or
+    (3 n + 3) // 4 for the packed F6E2M3 / F6E3M2."""
     if dtype == DType.F4E2M1:
         return (int(n) + 1) // 2
+    if dtype in FP6_DTYPES:
+        return (3 * int(n) + 3) // 4
     return int(n) * np.dtype(_HOST_DTYPE[dtype]).itemsize
 
 
 def refuse_fp4(who: str, *buckets) -> None:
-    """F4E2M1 buckets are valid in the MX calls alone: every other call refuses them before it reaches the library."""
+    """F4E2M1, F6E2M3 and F6E3M2 buckets are valid in the MX calls alone: every other call refuses them before it
+    reaches the library."""
     for b in buckets:
-        if getattr(b, "dtype", None) == DType.F4E2M1:
-            raise ValueError(f"{who}: F4E2M1 buckets are valid only in reduce_tree_mx, mx_quantize, mx_dequantize and "
+        dt = getattr(b, "dtype", None)
+        if dt == DType.F4E2M1 or dt in FP6_DTYPES:
+            raise ValueError(f"{who}: {DType(dt).name} buckets are valid only in reduce_tree_mx, mx_quantize, mx_dequantize and "
                              f"Comm.allreduce_mx")
 
 
@@ -144,6 +159,35 @@ def fp4_unpack(packed, n: int) -> np.ndarray:
     out[0::2] = b & 0xF
     out[1::2] = b >> 4
     return out[:int(n)]
+
+
+def fp6_pack(codes) -> np.ndarray:
+    """FP6 codes (one per element, 0..63) packed four to three bytes: element i in bits 6 i .. 6 i + 5 of the
+    little-endian bit string; the unused high bits of the last byte are 0."""
+    c = np.ascontiguousarray(codes, dtype=np.uint8).ravel()
+    if c.size and int(c.max()) > 63:
+        raise ValueError("fp6_pack: codes must be in 0..63")
+    n = c.size
+    q = np.zeros((n + 3) // 4 * 4, np.uint32)
+    q[:n] = c
+    q = q.reshape(-1, 4)
+    w = q[:, 0] | (q[:, 1] << 6) | (q[:, 2] << 12) | (q[:, 3] << 18)
+    out = np.stack([w & 0xFF, (w >> 8) & 0xFF, (w >> 16) & 0xFF], axis=1).astype(np.uint8).ravel()
+    return out[:(3 * n + 3) // 4].copy()
+
+
+def fp6_unpack(packed, n: int) -> np.ndarray:
+    """The n FP6 codes of a packed bucket ((3 n + 3) // 4 bytes): the inverse of fp6_pack."""
+    b = np.ascontiguousarray(packed, dtype=np.uint8).ravel()
+    n = int(n)
+    if b.size != (3 * n + 3) // 4:
+        raise ValueError(f"fp6_unpack: {n} elements are {(3 * n + 3) // 4} bytes, got {b.size}")
+    t = np.zeros((n + 3) // 4 * 3, np.uint32)
+    t[:b.size] = b
+    t = t.reshape(-1, 3)
+    w = t[:, 0] | (t[:, 1] << 8) | (t[:, 2] << 16)
+    out = np.stack([w & 63, (w >> 6) & 63, (w >> 12) & 63, (w >> 18) & 63], axis=1).astype(np.uint8).ravel()
+    return out[:n].copy()
 
 
 def dtype_of(arr_or_dtype) -> DType:
@@ -263,13 +307,18 @@ class Bucket:
 
     def view(self, offset: int, n: int) -> "Bucket":
         """Sub-bucket starting `offset` elements in (used to exercise unaligned buckets). An F4E2M1 bucket needs an even
-        element offset: a view starts on a byte."""
+        element offset, an F6E2M3 / F6E3M2 bucket a multiple of 4: a view starts on a byte."""
         if offset < 0 or offset + n > self.n:
             raise ValueError("view out of range")
         if self.dtype == DType.F4E2M1:
             if offset % 2:
                 raise ValueError("view: an F4E2M1 bucket needs an even element offset (two elements to a byte)")
             return Bucket(n, self.dtype, ptr=self.ptr + offset // 2, owner=self)
+        if self.dtype in FP6_DTYPES:
+            if offset % 4:
+                raise ValueError(f"view: an {self.dtype.name} bucket needs an element offset that is a multiple of 4 (four elements "
+                                 f"to three bytes)")
+            return Bucket(n, self.dtype, ptr=self.ptr + offset // 4 * 3, owner=self)
         return Bucket(n, self.dtype, ptr=self.ptr + offset * self.itemsize, owner=self)
 
     def upload(self, arr: np.ndarray, stream=None) -> None:
@@ -487,9 +536,9 @@ def _mx_scales(b, what: str, n: int) -> int:
 
 
 def _mx_elements(who: str, what: str, b: Bucket) -> DType:
-    if b.dtype not in (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1):
+    if b.dtype not in MX_DTYPES:
         raise ValueError(f"{who} needs F8E4M3 or F8E5M2 {what}, got {DType(b.dtype).name}; F4E2M1 (MXFP4) is the third "
-                         f"element type an MX bucket can have")
+                         f"element type an MX bucket can have, F6E2M3 and F6E3M2 (MXFP6) the fourth and fifth")
     return b.dtype
 
 
@@ -507,8 +556,9 @@ def _sr_seed(who: str, seed, out: Bucket, first: int) -> int:
 def reduce_tree_mx(op: Op, alg: Alg, out: Bucket, out_scales: Optional[Bucket], ins: Sequence[Bucket],
                    in_scales: Sequence[Bucket], rank: int = 0, stream=None, seed: Optional[Bucket] = None,
                    first: int = 0) -> None:
-    """The sum (Op.SUM) or mean (Op.AVG) of block-scaled (MX) F8E4M3 / F8E5M2 (MXFP8) or F4E2M1 (MXFP4, packed two
-    elements to a byte; the scale rule at EMAX = 2) buckets (fmi_dev_reduce_tree_mx): every
+    """The sum (Op.SUM) or mean (Op.AVG) of block-scaled (MX) F8E4M3 / F8E5M2 (MXFP8), F4E2M1 (MXFP4, packed two
+    elements to a byte; the scale rule at EMAX = 2) or F6E2M3 / F6E3M2 (MXFP6, packed four elements to three bytes; the
+    largest elements 7.5 and 28) buckets (fmi_dev_reduce_tree_mx): every
     input element times its block's E8M0 scale in f32, the f32 SUM program of `alg`, then either stored as F32 (`out` an
     F32 bucket, out_scales None) or requantized: per block of 32 the smallest power-of-two scale that brings the block's
     largest magnitude within the element type, into `out_scales`, and the scaled sum narrowed into `out`. in_scales[p]
@@ -555,14 +605,14 @@ def mx_quantize(out: Bucket, out_scales: Bucket, src: Bucket, stream=None, seed:
 
 def mx_quantize_sr_host(dtype, src, seed: int, first: int = 0):
     """fmi_dev_mx_quantize_sr of a float32 numpy array on the host (fmi_host_mx_quantize_sr): (element bytes, scale bytes)
-    as np.uint8 arrays, the bytes the device call stores for the same (seed, first). dtype: F8E4M3, F8E5M2 or F4E2M1
-    (packed, ceil(n / 2) bytes). Needs no device."""
+    as np.uint8 arrays, the bytes the device call stores for the same (seed, first). dtype: F8E4M3, F8E5M2, F4E2M1
+    (packed, ceil(n / 2) bytes) or F6E2M3 / F6E3M2 (packed, ceil(3 n / 4) bytes). Needs no device."""
     dtype = DType(dtype)
-    if dtype not in (DType.F8E4M3, DType.F8E5M2, DType.F4E2M1):
+    if dtype not in MX_DTYPES:
         raise ValueError(f"mx_quantize_sr_host needs F8E4M3, F8E5M2 or F4E2M1, got {dtype.name}")
     a = np.ascontiguousarray(src, np.float32).ravel()
     n = a.size
-    out = np.zeros((n + 1) // 2 if dtype == DType.F4E2M1 else n, np.uint8)
+    out = np.zeros(storage_bytes(dtype, n), np.uint8)
     scales = np.zeros(mx_blocks(n), np.uint8)
     if not 0 <= int(seed) < 1 << 64 or not 0 <= int(first) < 1 << 64:
         raise ValueError("mx_quantize_sr_host: seed and first are unsigned 64-bit values")
@@ -624,8 +674,8 @@ def host_reduce_pair(op: Op, inout: np.ndarray, src: np.ndarray, dtype: Optional
     if not (inout.flags.c_contiguous and src.flags.c_contiguous):
         raise ValueError("host_reduce_pair: arrays must be contiguous")
     dt = dtype_of(inout) if dtype is None else DType(dtype)
-    if dt == DType.F4E2M1:
-        raise ValueError("host_reduce_pair: F4E2M1 is valid only in the MX calls")
+    if dt == DType.F4E2M1 or dt in FP6_DTYPES:
+        raise ValueError(f"host_reduce_pair: {dt.name} is valid only in the MX calls")
     if np.dtype(_HOST_DTYPE[dt]).itemsize != inout.dtype.itemsize:
         raise ValueError("host_reduce_pair: the arrays' element size is not the dtype's")
     _lib.call("fmi_host_reduce_pair", int(op), int(dt), inout.ctypes.data, src.ctypes.data, inout.size)

@@ -145,12 +145,27 @@ typedef enum { FMI_OP_SUM = 0, FMI_OP_PROD = 1, FMI_OP_MAX = 2, FMI_OP_MIN = 3, 
  * The type is valid ONLY as the `dtype` of the four MX calls (fmi_dev_reduce_tree_mx, fmi_dev_mx_quantize,
  * fmi_dev_mx_dequantize, fmi_comm_allreduce_mx; there FMI_ACC_F32 on it is accepted and dropped). Every other entry
  * point that takes a dtype answers FMI_ERR_INVALID with a message naming FMI_F4E2M1, on the host. Additive:
- * fmi_abi_version() stays 1, no new symbol. */
+ * fmi_abi_version() stays 1, no new symbol.
+ *
+ * FMI_F6E2M3 = 16, FMI_F6E3M2 = 17: the two OCP 6-bit floats, the elements of an MXFP6 bucket. Six bits per element:
+ * bit 5 is the sign (so -0 exists, code 0x20); no inf, no NaN; the magnitude codes 0..31 ascend in value.
+ *   E2M3: 2 exponent bits (bias 1), 3 mantissa bits. Exponent field 0: m / 8 (0, 0.125 .. 0.875); otherwise
+ *         (1 + m / 8) * 2^(e - 1). The largest value is 7.5 = 1.875 * 2^2.
+ *   E3M2: 3 exponent bits (bias 3), 2 mantissa bits. Exponent field 0: m / 16 (0, 0.0625, 0.125, 0.1875); otherwise
+ *         (1 + m / 4) * 2^(e - 3). The largest value is 28 = 1.75 * 2^4.
+ * Packing: the bucket is a little-endian bit string, element i in bits 6 i .. 6 i + 5, bit j of the string being bit
+ * j mod 8 of byte j div 8. Four elements are three bytes, a block of 32 is 24 bytes, n elements take ceil(3 n / 4)
+ * bytes; the unused high bits of the last byte are ignored on input and written as 0 on output. Widen is the 64-entry
+ * table (exact in f32). Narrow is round-to-nearest on the 32 magnitudes with ties to the even CODE, the sign kept; it is
+ * defined for finite |y| <= the largest element only, which is all the MX calls feed it.
+ * Like FMI_F4E2M1, both are valid ONLY as the `dtype` of the MX calls (FMI_ACC_F32 on them is accepted and dropped
+ * there); every other entry point that takes a dtype, fmi_dev_fill_synthetic* included, answers FMI_ERR_INVALID with a
+ * message naming the type, on the host. Additive: fmi_abi_version() stays 1, no new symbol. */
 typedef enum {
     FMI_F32 = 0, FMI_F64 = 1, FMI_I32 = 2, FMI_I64 = 3,
     FMI_U32 = 4, FMI_U64 = 5, FMI_I8 = 6, FMI_U8 = 7, FMI_I16 = 8, FMI_U16 = 9,
     FMI_F16 = 10, FMI_BF16 = 11, FMI_F8E4M3 = 12, FMI_F8E5M2 = 13,
-    FMI_F4E2M1 = 15
+    FMI_F4E2M1 = 15, FMI_F6E2M3 = 16, FMI_F6E3M2 = 17
 } fmi_dtype_t;
 /* Reserved, NOT an fmi_dtype_t: FMI_F8E8M0 = 14 is the label the Python binding gives the scale bytes of an MX bucket
  * (DType.F8E8M0, bytes over np.uint8; fmi_dev_reduce_tree_mx below). No C-ABI call takes it as a dtype: every one
@@ -426,7 +441,22 @@ int fmi_dev_reduce_tree_scaled(int op, int dtype, int alg, int out_dtype, void* 
  *     rule a NaN scale makes the block NaN, and dequantizing it gives NaN by the multiply above).
  * out_dtype == FMI_F4E2M1 or FMI_F32; the fused kernel needs the element buckets 16-B aligned (a block of 32 elements is
  * one 16-B word); the fallback and the two conversions take any BYTE alignment. out may alias an input where the types
- * agree. No byte beyond ceil(n / 2) and no scale byte beyond ceil(n / 32) is touched. */
+ * agree. No byte beyond ceil(n / 2) and no scale byte beyond ceil(n / 32) is touched.
+ *
+ * MXFP6: dtype FMI_F6E2M3 or FMI_F6E3M2 (the encodings and the packing at fmi_dtype_t). A bucket of n elements is
+ * ceil(3 n / 4) element bytes and ceil(n / 32) scale bytes; n counts ELEMENTS in every MX call. The text above holds
+ * with these type-specific pieces:
+ *   - widen is the 64-entry table; e = 255 gives NaN for every code, zeros included; e = 0 is 2^-127;
+ *   - E2M3: e_out = 255 if f == 255, otherwise max( f - 2 + (m > 0x700000), 0 )   (7.5 = 1.875 * 2^2)
+ *     E3M2: e_out = 255 if f == 255, otherwise max( f - 4 + (m > 0x600000), 0 )   (28 = 1.75 * 2^4)
+ *     so a finite block has e_out <= 253 (E2M3) or <= 251 (E3M2), a normal inverse scale, and |S * inv| <= the largest
+ *     element;
+ *   - a block with e_out == 255 stores the scale byte 255 and every code 0; it dequantizes to NaN through the scale;
+ *   - stochastic rounding (below): narrow_sr with (M, EMIN) = (3, 0) for E2M3 and (2, -2) for E3M2; the stream
+ *     positions, first % 32 == 0 and the scale bytes are as for the other types.
+ * out_dtype == dtype or FMI_F32; the fused kernel needs the element buckets 16-B aligned (a lane takes two blocks, 48 B);
+ * the fallback and the two conversions take any BYTE alignment. out may alias an input where the types agree. No byte
+ * beyond ceil(3 n / 4) and no scale byte beyond ceil(n / 32) is touched. */
 int fmi_dev_reduce_tree_mx(int op, int dtype, int alg, int out_dtype, void* out, void* out_scales, const void* const* ins,
                            const void* const* in_scales, int P, int rank, size_t n, fmi_stream_t stream);
 /* The fallback's two kernels made public, as fmi_dev_convert is. The non-MX side (src_dtype / dst_dtype) is FMI_F32,
@@ -600,7 +630,9 @@ int fmi_comm_allreduce_scaled(fmi_comm_t comm, int op, int dtype, int alg, int o
  * enters a block's amax); element and scale shards are then all-gathered. Every rank's recv / recv_scales is the
  * definition over the ranks' buckets in rank order. send / send_scales are not modified. A one-rank communicator runs
  * the P = 1 form. FMI_F4E2M1: the same route at half the element bytes (a shard of 64 k elements is 32 k bytes); only the
- * last non-empty shard can have an odd true length. */
+ * last non-empty shard can have an odd true length. FMI_F6E2M3 / FMI_F6E3M2: the same route at three quarters of the
+ * element bytes (a shard of 64 k elements is 48 k bytes: whole blocks, whole bytes, 16-B aligned); only the last
+ * non-empty shard can be ragged. */
 int fmi_comm_allreduce_mx(fmi_comm_t comm, int op, int dtype, int alg, int out_dtype, const void* send,
                           const void* send_scales, void* recv, void* recv_scales, size_t n, fmi_stream_t stream);
 /* fmi_comm_allreduce_mx with stochastic rounding (fmi_dev_reduce_tree_mx_sr above): the same route, the output of the

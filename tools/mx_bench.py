@@ -29,6 +29,20 @@ Bytes with the scale bytes counted: inputs P * (n / 2 + n / 32), output n / 2 + 
 
     python3 tools/mx_bench.py --kind e2m1 [--label NAME] [--out profiles/mxfp4_bench.jsonl]
 
+--kind e2m3 / --kind e3m2: the fused MXFP6 kernel (FMI_F6E2M3 / FMI_F6E3M2 elements, four to three bytes) by the same
+protocol, with the unchanged fused MXFP8 E4M3 kernel as the yardstick, in the same passes and at the same ELEMENT count:
+
+  mx                reduce_tree_mx on E4M3 buckets, out = E4M3 with scale bytes (the yardstick)
+  mxfp6             reduce_tree_mx on FP6 buckets, out = FP6 with scale bytes: the fused kernel
+  mx_f32            the yardstick's kernel with an F32 output: what mxfp6_f32 stands beside (both store 4 n bytes)
+  mxfp6_f32         the fused MXFP6 kernel with an F32 output
+  mxfp6_sr          the fused MXFP6 kernel with stochastic rounding
+  mxfp6_fallback    the same buckets three bytes off 16-B alignment
+
+Bytes with the scale bytes counted: inputs P * (3 n / 4 + n / 32), output 3 n / 4 + n / 32 or 4 n.
+
+    python3 tools/mx_bench.py --kind e2m3 [--label NAME] [--out profiles/mxfp6_bench.jsonl]
+
 --sr: the stochastic-rounding kernels (fmi_dev_reduce_tree_mx_sr) beside the round-to-nearest ones, whose code is
 unchanged, in the same passes at the same element count:
 
@@ -124,6 +138,75 @@ def main_e2m1(args):
     fmi_amd.sync()
 
 
+FP6_ROWS = ("mx", "mxfp6", "mx_f32", "mxfp6_f32", "mxfp6_sr", "mxfp6_fallback")  # the first is the yardstick
+
+
+def main_fp6(args):
+    """n ELEMENTS per peer: E4M3 buckets of n bytes for the yardstick, FP6 buckets of 3 n / 4 bytes."""
+    P, n, S = args.peers, args.mib * MIB, args.sets
+    dt = DType.F6E2M3 if args.kind == "e2m3" else DType.F6E3M2
+    nb = fmi_amd.mx_blocks(n)
+    rows = [r for r in FP6_ROWS if r == FP6_ROWS[0] or r in args.rows.split(",")]
+    g8 = [Bucket.group(P + 1, n, DType.F8E4M3) for _ in range(S)]
+    # 48 spare bytes (64 elements) per bucket: the fallback's buckets are the same allocations three bytes in
+    g6 = [Bucket.group(P + 1, n + 64, dt) for _ in range(S)]
+    aligned = [[b.view(0, n) for b in g] for g in g6]
+    shifted = [[b.view(4, n) for b in g] for g in g6]
+    wide = [Bucket(n, np.float32) for _ in range(S)]
+    seed = Bucket.from_numpy(np.array([0x0123456789ABCDEF], np.uint64))
+    rng = np.random.default_rng(3)
+    packed = rng.integers(0, 256, n // 4 * 3 + 48, dtype=np.uint8)  # every code; the buckets differ by a flip of code bits
+    scale_sets = []
+    for k in range(S):
+        for p in range(P):
+            g8[k][p].fill_synthetic(11, p)
+            g6[k][p].upload(packed ^ np.uint8(17 * (k * P + p) & 0xFF))
+        scale_sets.append([Bucket(nb, DType.F8E8M0) for _ in range(P + 1)])
+        for b in scale_sets[-1][:P]:
+            b.upload(rng.integers(120, 135, nb).astype(np.uint8))
+    fmi_amd.sync()
+    tree = lambda out, osc, ins, k, **kw: fmi_amd.reduce_tree_mx(Op.SUM, Alg.ALLREDUCE, out, osc, ins, scale_sets[k % S][:P], **kw)  # noqa: E731
+    launches = {
+        "mx": lambda k: tree(g8[k % S][P], scale_sets[k % S][P], g8[k % S][:P], k),
+        "mxfp6": lambda k: tree(aligned[k % S][P], scale_sets[k % S][P], aligned[k % S][:P], k),
+        "mx_f32": lambda k: tree(wide[k % S], None, g8[k % S][:P], k),
+        "mxfp6_f32": lambda k: tree(wide[k % S], None, aligned[k % S][:P], k),
+        "mxfp6_sr": lambda k: tree(aligned[k % S][P], scale_sets[k % S][P], aligned[k % S][:P], k, seed=seed, first=0),
+        "mxfp6_fallback": lambda k: tree(shifted[k % S][P], scale_sets[k % S][P], shifted[k % S][:P], k),
+    }
+    e6 = n // 4 * 3
+    algo = {"mx": P * (n + nb) + n + nb, "mx_f32": P * (n + nb) + 4 * n, "mxfp6": P * (e6 + nb) + e6 + nb, "mxfp6_f32": P * (e6 + nb) + 4 * n,
+            "mxfp6_sr": P * (e6 + nb) + e6 + nb, "mxfp6_fallback": P * (e6 + nb) + e6 + nb}
+    iters = {r: args.fallback_iters if r == "mxfp6_fallback" else args.iters for r in FP6_ROWS}
+    ms = {r: [] for r in rows}
+    for _ in range(PASSES):
+        for r in rows:
+            ms[r].append(timed(launches[r], iters[r], S))
+    spread = lambda xs: round((max(xs) - min(xs)) / statistics.median(xs), 4)  # noqa: E731
+    elem = {r: [n / (m * 1e-3) for m in ms[r]] for r in rows}
+    lines = []
+    for r in rows:
+        byte_rate = [algo[r] / (m * 1e-3) for m in ms[r]]
+        ratios = [a / b for a, b in zip(elem[r], elem[FP6_ROWS[0]])]
+        lines.append({"tool": f"tools/mx_bench.py --kind {args.kind}", "label": args.label, "inflight_kib": fmi_amd.tune_get(fmi_amd.Tune.FUSED_INFLIGHT_KIB),
+                      "kernel": f"tree{P} {'e4m3' if r in ('mx', 'mx_f32') else args.kind} {r}", "elements_per_peer": n, "algorithmic_bytes": algo[r],
+                      "bytes_per_element": round(algo[r] / n, 4),
+                      "iters_per_pass": iters[r], "passes": PASSES, "rotating_sets": S, "ms_per_pass": [round(m, 4) for m in ms[r]],
+                      "ms_per_call": round(statistics.median(ms[r]), 4),
+                      "Gelem_s_per_pass": [round(x / 1e9, 2) for x in elem[r]], "Gelem_s": round(statistics.median(elem[r]) / 1e9, 2),
+                      "GB_s_per_pass": [round(x / 1e9, 1) for x in byte_rate], "GB_s": round(statistics.median(byte_rate) / 1e9, 1),
+                      "fraction_of_8TBs": round(statistics.median(byte_rate) / PEAK, 4), "spread": spread(byte_rate),
+                      "yardstick": f"tree{P} e4m3 mx (the fused MXFP8 kernel), same passes, same element count, element rate",
+                      "element_rate_ratio_to_mxfp8_per_pass": [round(x, 4) for x in ratios],
+                      "element_rate_ratio_to_mxfp8": round(statistics.median(ratios), 4),
+                      "at_least_mxfp8_in_every_pass": all(x >= 1.0 for x in ratios), "mxfp8_spread": spread(elem[FP6_ROWS[0]]),
+                      "timing": "two HIP events around back-to-back launches on the library stream"})
+    emit(lines, args.out)
+    for b in [b for g in g8 + g6 for b in g] + wide + [b for s in scale_sets for b in s] + [seed]:
+        b.free()
+    fmi_amd.sync()
+
+
 SR_ROWS = ("mx", "mxfp4", "mx_sr", "mxfp4_sr", "mx_f32_then_quantize_sr", "mxfp4_f32_then_quantize_sr")
 SR_YARDSTICK = {"mx": "mx", "mxfp4": "mxfp4", "mx_sr": "mx", "mxfp4_sr": "mxfp4", "mx_f32_then_quantize_sr": "mx",
                 "mxfp4_f32_then_quantize_sr": "mxfp4"}
@@ -204,7 +287,7 @@ def main_sr(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", default="e4m3", choices=("e4m3", "e5m2", "e2m1"))
+    ap.add_argument("--kind", default="e4m3", choices=("e4m3", "e5m2", "e2m1", "e2m3", "e3m2"))
     ap.add_argument("--mib", type=int, default=256, help="element bytes per input bucket")
     ap.add_argument("--peers", type=int, default=8)
     ap.add_argument("--sets", type=int, default=3)
@@ -222,6 +305,10 @@ def main():
         if args.rows == ",".join(ROWS):
             args.rows = ",".join(FP4_ROWS)
         return main_e2m1(args)
+    if args.kind in ("e2m3", "e3m2"):
+        if args.rows == ",".join(ROWS):
+            args.rows = ",".join(FP6_ROWS)
+        return main_fp6(args)
     dt = DType.F8E4M3 if args.kind == "e4m3" else DType.F8E5M2
     P, n, S = args.peers, args.mib * MIB, args.sets
     nb = fmi_amd.mx_blocks(n)
